@@ -8,7 +8,10 @@ KV, batch 64 per GPU (BASELINE.json configs[1]); synthetic Philox weights and PC
 offline).  Before the warmup an UNTIMED fill of `context` steps brings every slot's ring cache to
 steady state, so each timed step streams the whole 750-frame KV cache.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+      A plain run sets up, fills the rings, warms up, times K steps and prints the headline line; --dump-outputs also
+      writes what the last timed step returned as DIR/<name>.npy.  --full adds every other measurement (roofline passes,
+      capacity / host-path / other-configuration legs, dot_mode agreement, CPU baseline) to the line.
       N > 1 without a launcher: spawns N ranks itself (python -m torch.distributed.run ... bench.py, as child
       processes, before this process imports torch); under a launcher (WORLD_SIZE set) it is one of the ranks.
 
@@ -35,6 +38,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="stream slots per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the roofline / per-class profiling "
+                         "passes, capacity and host-path legs, the other dot_mode, the other configurations, the dot_mode agreement pass, "
+                         "the CPU baseline and (--workload tts) the guided leg; the options below that select or skip those legs only "
+                         "matter with --full")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (stt: codes, text_tokens, vad_probs; "
+                         "mimi-decode: pcm; tts: text_tokens, audio_tokens) as DIR/<name>.npy (float32; integer tokens and codes as float64); inputs are seeded, so two "
+                         "builds run with the same arguments can be compared array for array")
     ap.add_argument("--config", default="stt-1b-en_fr", choices=["stt-1b-en_fr", "stt-2.6b-en", "tiny"])
     ap.add_argument("--dot-mode", type=int, default=1, choices=[0, 1],
                     help="dsm_asr_config.dot_mode of the timed engine.  1 (bench default): the LM's bf16-weight GEMMs on v_mfma_f32_16x16x32_bf16 "
@@ -70,6 +82,18 @@ def parse():
     return ap.parse_args()
 
 
+def dump_outputs(args, world, rank, arrays):
+    """--dump-outputs: one .npy per returned array, float32 for floating-point outputs and float64 for integer tokens /
+    codes (exact for every uint32); with several ranks each writes its own `<name>.rank<r>.npy`."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(args.dump_outputs, name + ("" if world == 1 else ".rank%d" % rank) + ".npy"),
+                a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def other_config_leg(args, spec):
     """One of the other BASELINE.json configurations as a child `bench.py` run on the same GPU (its own engine and a synthetic
     checkpoint in a scratch directory that is deleted afterwards); returns the fields VERDICT r03 #4 asks for."""
@@ -77,7 +101,7 @@ def other_config_leg(args, spec):
     import tempfile
     name, batch = spec.split(":")
     wd = tempfile.mkdtemp(prefix="dsm_other_", dir=os.path.dirname(args.weights_dir.rstrip("/")) or "/tmp")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", batch, "--steps", "30", "--warmup", "5", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", batch, "--steps", "30", "--warmup", "5", "--no-cpu-baseline",
            "--capacity-legs", "", "--host-path-legs", "", "--other-configs", "", "--no-agreement", "--dot-mode", str(args.dot_mode), "--weights-dir", wd]
     cmd += ["--workload", "tts"] if name == "tts" else ["--config", name, "--fast-fill"]
     try:
@@ -159,6 +183,7 @@ def bench_decode(args, eng, cfg, B, dev, world, rank, dist, torch):
         it += 1
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1000
+    dump_outputs(args, world, rank, {"pcm": pcm.cpu().numpy().reshape(B, 1920)})
     if rank == 0:
         print(json.dumps({"metric": "Mimi decode_step real-time stream throughput @ bs=%d" % B, "value": world * B * 0.08 / (ms / 1000),
                           "unit": "x realtime (stream-seconds of audio per wall second)", "n_gpus": world, "steps": args.steps,
@@ -184,6 +209,8 @@ def bench_tts(args, world, rank, local_rank):
     fill = cfg.text_audio_delay_in_tokens + cfg.acoustic_delay + 3  # past both delay windows: every codebook feeds back
     SRC_ROWS = 125  # speaker_cond_n_speakers (5) x 2 s at 12.5 Hz: what the server's conditioner hands State::new (srv/tts.rs:426-441)
 
+    last = [None]  # what the latest step returned: (text tokens, audio tokens)
+
     def run(c, guided, steps, warmup):
         eng = dsm_amd.TtsEngine(c, B, path, device_id=local_rank)
         empty = synth.synth_ca_src(c, SRC_ROWS, 9)
@@ -196,7 +223,7 @@ def bench_tts(args, world, rank, local_rank):
         def step():
             prev = rng.integers(4, c.text_in_vocab_size - 1, B).astype(np.uint32)
             allowed = rng.integers(4, c.text_in_vocab_size - 1, B).astype(np.int32)
-            eng.step(prev, allowed, mask)
+            last[0] = eng.step(prev, allowed, mask)
 
         for _ in range(fill + warmup):
             step()
@@ -217,8 +244,9 @@ def bench_tts(args, world, rank, local_rank):
         return float(dt.item()) / steps * 1000, m
 
     ms, m = run(cfg, False, args.steps, args.warmup)
+    dump_outputs(args, world, rank, {"text_tokens": last[0][0], "audio_tokens": last[0][1]})
     guided = None
-    if args.tts_guided_leg and world == 1:
+    if args.full and args.tts_guided_leg and world == 1:
         gcfg = type(cfg).from_buffer_copy(cfg)
         gcfg.cfg_rows = 1
         gms, _ = run(gcfg, True, min(args.steps, 20), 3)
@@ -355,6 +383,35 @@ def capacity_leg(dsm_amd, synth, cfg, B, arena, dev, local_rank, steps, torch):
         eng.close()
 
 
+def headline(args, cfg, B, world, ms_per_step, fill, groups, fan, per_rank_ms):
+    """The fields of the result line that the timed steps alone determine (a plain run prints exactly these)."""
+    return {
+        "metric": "real-time stream throughput, %s @ bs=%d per GPU (Mimi encode + LM decode per 80 ms frame)" % (args.config, B),
+        "value": world * B * 0.08 / (ms_per_step / 1000.0),
+        "unit": "x realtime (stream-seconds of audio per wall second)",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak",
+        # BASELINE.md's published figure for this metric: 64 streams @ 3x real time = 192 x realtime at batch_size 64,
+        # on 1x NVIDIA L40S (reference README.md:73-74) — other hardware, quoted for scale only
+        "vs_baseline": (B * 0.08 / (ms_per_step / 1000.0)) / 192.0 if (args.config == "stt-1b-en_fr" and B == 64) else None,
+        "baseline": "64 streams @ 3x real time (192 x realtime) on 1x L40S, per GPU (BASELINE.md)",
+        "dtype": ("bf16 weights + bf16 KV, f32 activations as three exact bf16 pieces, f32 accumulate (v_mfma_f32_16x16x32_bf16)"
+                  if args.dot_mode == 1 else "bf16 weights + bf16 KV, f32 activations/accumulate (v_mfma_f32_16x16x4_f32)"),
+        "data": "synthetic", "dot_mode": args.dot_mode,
+        "rtf": 80.0 / ms_per_step,
+        "config": {"workload": "%s batch=%d streaming, ring KV cache full (%d frames), Mimi encode + LM decode HIP path"
+                               % (args.config, B, fill),
+                   "streams_per_gpu": B, "parallelism": "replicas x%d (independent stream batches, no per-step collective)" % world,
+                   "streams": "single stream" if args.no_overlap else "encoder stream || %d LM group stream(s)" % len(groups),
+                   "rccl_ranks": world if world > 1 else None,
+                   "weights_broadcast_ms": fan["broadcast_ms"] if fan else None,
+                   "weights_broadcast_bytes": fan["arena_bytes"] if fan else None,
+                   "weights_broadcast_gbps": (fan["arena_bytes"] / (fan["broadcast_ms"] * 1e-3) / 1e9) if fan and fan["broadcast_ms"] > 0 else None,
+                   "per_rank_ms_per_step": per_rank_ms,
+                   "weights_broadcast": "packed device weight arena, rank 0 -> all, RCCL over xGMI, once at load" if fan else None},
+    }
+
+
 def main():
     args = parse()
     world_env = os.environ.get("WORLD_SIZE")
@@ -450,6 +507,18 @@ def main():
     dt = float(dt_t.item())
     ms_per_step = dt / args.steps * 1000.0
     per_rank_ms = rank_report(dist, torch, dev, own_ms, eng.weight_arena()[1]) if world > 1 else [own_ms]
+    # what the last timed step handed back, copied out before any later pass steps over the same buffers
+    dump_outputs(args, world, rank, {"codes": codes.cpu().numpy().reshape(B, cfg.audio_codebooks), "text_tokens": text.cpu().numpy(),
+                                     "vad_probs": prs.cpu().numpy().reshape(-1, B)} if args.dump_outputs else {})
+    fill = ctx if not args.no_fill else min(it[0], ctx)
+    if not args.full:  # a plain run ends here: the headline line and nothing that takes steps of its own
+        if rank == 0:
+            print(json.dumps(headline(args, cfg, B, world, ms_per_step, fill, eng.stream_groups(), fan, per_rank_ms)))
+        eng.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- separate pass (not part of `value`): the dominant kernel bracketed live, i.e. with the other streams running
     # beside it — HIP events on the stream it is launched on + the in-kernel device-clock bracket ----
@@ -542,7 +611,6 @@ def main():
     if rank == 0:
         H, hd, L = cfg.lm.num_heads, cfg.lm.d_model // cfg.lm.num_heads, cfg.lm.num_layers
         kv_b = 2 if cfg.kv_bf16 else 4
-        fill = ctx if not args.no_fill else min(it[0], ctx)
         # algorithmic bytes of the attention launches of ONE layer: K and V of every (slot, head) once + q in + out.
         # The LM step runs the batch as len(groups) stream groups, each with its own attention launch per layer, so a
         # launch covers B / len(groups) slots on average and `achieved` is bytes of all timed launches / their time.
@@ -580,31 +648,8 @@ def main():
         iso_avg_us = iso_dev["attn_lm"][0] / max(iso_dev["attn_lm"][1], 1) or float("nan")  # --part enc: no LM attention ran
         ok_legs = [b for b, v in legs.items() if "rtf" in v and v["rtf"] >= 1.0]
         out = {
-            "metric": "real-time stream throughput, %s @ bs=%d per GPU (Mimi encode + LM decode per 80 ms frame)" % (args.config, B),
-            "value": world * B * 0.08 / (ms_per_step / 1000.0),
-            "unit": "x realtime (stream-seconds of audio per wall second)",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak",
-            # BASELINE.md's published figure for this metric: 64 streams @ 3x real time = 192 x realtime at batch_size 64,
-            # on 1x NVIDIA L40S (reference README.md:73-74) — other hardware, quoted for scale only
-            "vs_baseline": (B * 0.08 / (ms_per_step / 1000.0)) / 192.0 if (args.config == "stt-1b-en_fr" and B == 64) else None,
-            "baseline": "64 streams @ 3x real time (192 x realtime) on 1x L40S, per GPU (BASELINE.md)",
-            "dtype": ("bf16 weights + bf16 KV, f32 activations as three exact bf16 pieces, f32 accumulate (v_mfma_f32_16x16x32_bf16)"
-                      if args.dot_mode == 1 else "bf16 weights + bf16 KV, f32 activations/accumulate (v_mfma_f32_16x16x4_f32)"),
-            "data": "synthetic", "dot_mode": args.dot_mode, "other_dot_mode": other_mode,
-            "rtf": 80.0 / ms_per_step,
-            "config": {"workload": "%s batch=%d streaming, ring KV cache full (%d frames), Mimi encode + LM decode HIP path"
-                                   % (args.config, B, fill),
-                       "streams_per_gpu": B, "parallelism": "replicas x%d (independent stream batches, no per-step collective)" % world,
-                       "streams": "single stream" if args.no_overlap else "encoder stream || %d LM group stream(s)" % len(groups),
-                       "rccl_ranks": world if world > 1 else None,
-                       "weights_broadcast_ms": fan["broadcast_ms"] if fan else None,
-                       "weights_broadcast_bytes": fan["arena_bytes"] if fan else None,
-                       "weights_broadcast_gbps": (fan["arena_bytes"] / (fan["broadcast_ms"] * 1e-3) / 1e9) if fan and fan["broadcast_ms"] > 0 else None,
-                       "per_rank_ms_per_step": per_rank_ms,
-                       "weights_broadcast": "packed device weight arena, rank 0 -> all, RCCL over xGMI, once at load" if fan else None,
-                       "timed_region": "instrumentation off; roofline brackets come from a separate %d-step pass (%.3f ms/step with the brackets on)"
-                                       % (n_prof, dt_prof / n_prof * 1000.0)},
+            **headline(args, cfg, B, world, ms_per_step, fill, groups, fan, per_rank_ms),
+            "other_dot_mode": other_mode,
             "roofline": {"bound": "hbm", "kernel": "attn_kernel<bf16,hd%d,T1> (LM ring-cache attention%s, %d launches/step: %d layers x %d stream groups of %s slots)"
                                                     % (hd, " with the fused QKV reduce + RoPE + ring scatter prologue" if fused else "", L * len(groups), L, len(groups), "/".join(str(n) for _, n in groups)),
                          "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
@@ -619,6 +664,8 @@ def main():
             "whole_step": {"algorithmic_bytes": step_bytes, "achieved": step_bytes / (ms_per_step * 1e-3) / 1e9, "unit": "GB/s",
                            "frac_of_hbm_peak": step_bytes / (ms_per_step * 1e-3) / 1e9 / 8000.0},
         }
+        out["config"]["timed_region"] = ("instrumentation off; roofline brackets come from a separate %d-step pass (%.3f ms/step with the brackets on)"
+                                         % (n_prof, dt_prof / n_prof * 1000.0))
         if legs:
             out["capacity"] = {"legs": {str(b): v for b, v in legs.items()},
                                "streams_at_rtf_ge_1": max(ok_legs) if ok_legs else None,

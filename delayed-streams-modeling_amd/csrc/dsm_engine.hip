@@ -223,7 +223,10 @@ struct dsm_engine {
   bool bx3_nt2 = true;        // DSM_BX3_NT2=0: one n-tile per wave in the whole-K bx3 kernel's plain-epilogue launches
   int dot_mode = 0;           // dsm_asr_config.dot_mode / dsm_tts_config.dot_mode: 1 = the bf16-weight GEMMs in "bx3" (gemm_bx3_kernel)
   int attn_nt = 1;            // DSM_ATTN_NT: ring-cache rows with non-temporal loads: 0 never, 1 bf16 rings (default), 2 every ring
-  bool fuse_front = true;     // DSM_FUSE_FRONT=0: the SEANet front end as three GEMM launches (r01)
+  // DSM_FUSE_FRONT=1: the SEANet front end as one fused kernel (seanet_front_kernel) instead of three GEMM launches.  Off by
+  // default: with the fused kernel in the encoder stream, an encode that overlaps the LM's dot_mode 1 kernels on the same CUs
+  // emits codes that differ from run to run; the three launches are bit-reproducible and cost ~2 % per step
+  bool fuse_front = false;
   int smallk_loop = 1;        // DSM_SMALLK_LOOP=0: one-chunk GEMMs (K <= 256) over many m-tiles stay on gemm_tile_kernel (r01)
   int smallk_min_tiles = 1024;  // DSM_SMALLK_MIN: from how many 64-row tiles on
   int smallk_mt = 4;          // DSM_SMALLK_MT: 16-row tiles per workgroup of those launches

@@ -10,6 +10,7 @@ import json
 import os
 import struct
 import zlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -68,9 +69,21 @@ def write_safetensors(path, spec, dtype, seed=SEED):
     with open(tmp, "wb") as f:
         f.write(struct.pack("<Q", len(hj)))
         f.write(hj)
-        for name, shape, kind, param in spec.items:
-            a = _gen(name, shape, kind, param, seed)
-            f.write(f32_to_bf16_bits(a).tobytes() if dtype == "BF16" else a.tobytes())
+        def encode(item):
+            a = _gen(item[0], item[1], item[2], item[3], seed)
+            return f32_to_bf16_bits(a).tobytes() if dtype == "BF16" else a.tobytes()
+
+        # every tensor has its own Philox stream, so tensors are generated on a few threads (numpy releases the GIL) and
+        # written in file order: the bytes are those of the one-at-a-time loop; at most 2 * workers tensors are in memory
+        workers = max(1, min(8, len(os.sched_getaffinity(0))))
+        with ThreadPoolExecutor(workers) as pool:
+            pending = []
+            for item in spec.items:
+                pending.append(pool.submit(encode, item))
+                if len(pending) >= 2 * workers:
+                    f.write(pending.pop(0).result())
+            for fut in pending:
+                f.write(fut.result())
     os.replace(tmp, path)
 
 

@@ -5,6 +5,6 @@ ms() { python3 -c "import sys,json; j=json.loads([l for l in sys.stdin if l.star
 for round in 1 2; do
   for v in A B; do
     cp experiments/ab/lib$v.so $L
-    echo "$v tts (plain, guided) $(python bench.py --workload tts --batch 32 --steps 50 --warmup 5 2>/dev/null | ms)"
+    echo "$v tts (plain, guided) $(python bench.py --full --workload tts --batch 32 --steps 50 --warmup 5 2>/dev/null | ms)"
   done
 done

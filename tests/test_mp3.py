@@ -9,7 +9,7 @@ reference's decoder.  What these tests pin instead:
     > 80 dB; the IMDCT equals its defining sum and cancels time-domain aliasing against a numpy MDCT;
   * a numpy mini ENCODER (analysis bank, MDCT, alias butterflies, quantiser, Huffman writer with these tables: long blocks,
     linbits, count1 region) round-trips three tones through the whole decoder: > 55 dB;
-  * on the reference's own files (two as committed fixtures, all five where /root/reference is present): the frame walk finds
+  * on the reference's own files (all five committed under tests/golden/audio/, plus the head of one): the frame walk finds
     every frame the size implies, loses sync nowhere, every granule's Huffman data ends inside its part2_3_length, the PCM is
     frames x 1152 samples of band-limited speech (energy above 19 kHz < 1e-8 of the total, no clicks at granule boundaries);
   * the resampler: unit DC gain, a tone keeps frequency and level, a tone above the new Nyquist is gone (> 80 dB)."""
@@ -330,12 +330,11 @@ def test_bria_head_mp3_the_clip_of_baseline_config_0(dsm, lib):
     assert np.allclose(tail[k - 115200:], pcm[k:], atol=1e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/audio"), reason="the reference tree is only present in the build container")
 def test_every_mp3_the_reference_ships(dsm, lib):
     facts = json.load(open(os.path.join(AUD, "mp3_facts.json")))
     import hashlib
     for name, f in facts.items():
-        data = open(os.path.join("/root/reference/audio", name), "rb").read()
+        data = open(os.path.join(AUD, name), "rb").read()
         assert len(data) == f["bytes"] and hashlib.sha256(data).hexdigest() == f["sha256"]
         frames = f.get("frames_from_size", f["probe"]["frames"])
         _check_decode(dsm, data, frames)

@@ -58,7 +58,7 @@ def test_full_size_encode_lm_and_decode(gpu, dsm, lib, orc, full_weights, monkey
 @pytest.mark.parametrize("fuse_front", ["1", "0"])
 def test_seanet_front_fused_and_as_three_launches(gpu, dsm, lib, orc, full_weights, monkeypatch, fuse_front):
     """The real Mimi front end — init conv (1 -> 64, k 7), residual block (64 -> 32 k 3 -> 64 k 1, skip) — runs as one kernel
-    with its intermediates in LDS (`seanet_front_kernel`, default) or as three GEMM launches (DSM_FUSE_FRONT=0): both must give
+    with its intermediates in LDS (`seanet_front_kernel`, DSM_FUSE_FRONT=1) or as three GEMM launches (the default): both must give
     the oracle's latents and codes bit for bit over several frames (carried conv frames cross every frame boundary: the fused
     kernel reads them from the k-3 conv's buffer prefix and leaves the newest two frames in its tail), with a paused slot whose
     carried frames must not move, a mid-stream reset, and B = 5 so that tiles of different slots interleave."""
