@@ -207,39 +207,22 @@ struct dsm_engine {
   static constexpr int kMaxGroups = 4;
   hipStream_t s_grp[kMaxGroups] = {nullptr, nullptr, nullptr, nullptr};  // s_grp[0] is unused (group 0 runs on s_model)
   hipEvent_t ev_fork = nullptr, ev_grp_in[kMaxGroups] = {}, ev_grp_done[kMaxGroups] = {}, ev_stagger[kMaxGroups] = {};
-  bool stagger = true;  // DSM_STAGGER=0: every group starts its step at once (r01); 2: staggered at every batch size
-  bool stagger_force = false;
   bool grp_busy = false;
-  int enc_cus = 0;            // DSM_ENC_CUS: CUs per XCD for the encoder stream (0: no CU mask)
-  bool lm_cus_excl = false;   // DSM_LM_CUS_EXCL=1: the LM streams get the complement
-  bool fuse_qkv = true;  // DSM_FUSE_QKV=0: keep the separate QKV reduce launch
-  bool chunk_loop = true;  // DSM_CHUNK_LOOP=0: always split K across workgroups
-  bool roll_prefetch = true;  // DSM_ROLL=0: the chunk loop requests a chunk only after finishing the previous one (r01 behaviour)
-  size_t gemm_lds_pad = 0;    // DSM_GEMM_LDS_PAD (bytes)
-  bool gate_occ3 = false;     // DSM_GATE_OCC3=1: the gate's whole-K kernel squeezed to 168 VGPRs (three waves per SIMD, 80 B of spills)
-  int loop_depth = 4;         // DSM_LOOP_DEPTH=2: two-block rolling window (fewer registers, three waves per SIMD) where four is the default
-  size_t attn_lds_pad = 60000;  // DSM_ATTN_LDS_PAD: extra dynamic LDS per attention workgroup of a large launch (2 per CU)
-  int bx3_nt2_min = 256;      // ... from this many workgroups on (DSM_BX3_NT2_MIN)
-  bool bx3_nt2 = true;        // DSM_BX3_NT2=0: one n-tile per wave in the whole-K bx3 kernel's plain-epilogue launches
-  int dot_mode = 0;           // dsm_asr_config.dot_mode / dsm_tts_config.dot_mode: 1 = the bf16-weight GEMMs in "bx3" (gemm_bx3_kernel)
-  int attn_nt = 1;            // DSM_ATTN_NT: ring-cache rows with non-temporal loads: 0 never, 1 bf16 rings (default), 2 every ring
+  // ---- the ten DSM_* environment variables (read by dsm_read_env below, listed in include/dsm.h) and what they start from ----
+  bool use_graphs = true;       // DSM_GRAPHS=0: every launch sequence stays eager (GraphSlot below)
+  bool fuse_qkv = true;         // DSM_FUSE_QKV=0: keep the separate QKV reduce launch
+  bool stream_prio = false;     // DSM_STREAM_PRIO=1: LM streams high, encoder stream low (STT engine)
   // DSM_FUSE_FRONT=1: the SEANet front end as one fused kernel (seanet_front_kernel) instead of three GEMM launches.  Off by
   // default: with the fused kernel in the encoder stream, an encode that overlaps the LM's dot_mode 1 kernels on the same CUs
   // emits codes that differ from run to run; the three launches are bit-reproducible and cost ~2 % per step
   bool fuse_front = false;
-  int smallk_loop = 1;        // DSM_SMALLK_LOOP=0: one-chunk GEMMs (K <= 256) over many m-tiles stay on gemm_tile_kernel (r01)
-  int smallk_min_tiles = 1024;  // DSM_SMALLK_MIN: from how many 64-row tiles on
-  int smallk_mt = 4;          // DSM_SMALLK_MT: 16-row tiles per workgroup of those launches
-  int chunk_loop_min_tiles = 384;  // DSM_CHUNK_LOOP_MIN (swept at B = 512 / 1024: 384 best)
-  bool bx3u = true;           // DSM_BX3U=0: split-K bx3 launches at M <= 32 keep r03's one-block look-ahead (gemm_bx3_kernel)
-  bool wk_norm = false;       // DSM_WK_NORM=1: where the MLP input GEMM runs whole-K, norm2 moves into its prologue (gemm_wkn_kernel) and out_proj
-                              // stores the residual stream itself (two launches fewer per layer; measured 6.56 against 6.45 ms per TTS step: off)
-  int wk_gate_max_chunks = 4; // DSM_WK_GATE_CHUNKS: gated-MLP input GEMMs with at most this many K-chunks run whole-K-in-the-workgroup
-  bool bx3u_m64 = true;  // DSM_BX3U_M64=0: 33..64-row narrow GEMMs stay on one 64-row tile
-  bool bx3u_late = true;  // DSM_BX3U_LATE=0: the 32-row gemm_bx3u_kernel requests all eight weight blocks up front (129-140 VGPRs)
-  int attn_unr = 0;  // DSM_ATTN_UNR=4 / 8: force the bf16-ring attention kernel's keys per lane group and batch (0: by shape)
-  bool attn_small = true;  // DSM_ATTN_SMALL=0: rings of at most 32 positions use attn_kernel too
-                              // (gemm_wk_kernel: no slabs, no reduce launch); 0: never
+  int chunk_loop_min_tiles = 384;  // DSM_CHUNK_LOOP_MIN: whole-K workgroups from this many (n, m) tiles on (swept at B = 512 / 1024: 384 best)
+  int loop_depth = 4;           // DSM_LOOP_DEPTH=2: two-block rolling window (fewer registers, three waves per SIMD) where four is the default
+  int smallk_min_tiles = 1024;  // DSM_SMALLK_MIN: one-chunk GEMMs (K <= 256) move to gemm_loop_kernel from this many 64-row tiles on
+  int smallk_mt = 4;            // DSM_SMALLK_MT: 16-row tiles per workgroup of those launches
+  // ---- fixed per engine and dot_mode (dsm_read_env) ----
+  size_t attn_lds_pad = 60000;  // extra dynamic LDS per attention workgroup of a large launch (2 per CU; 40000 = 3 per CU)
+  int dot_mode = 0;             // dsm_asr_config.dot_mode / dsm_tts_config.dot_mode: 1 = the bf16-weight GEMMs in "bx3" (gemm_bx3_kernel)
   int prio_hi = 0;
   bool serialize_groups = false;  // dsm_debug_serialize_groups: every group on the model stream (profiling aid)
   hipEvent_t ev_codes_consumed = nullptr;
@@ -288,7 +271,6 @@ struct dsm_engine {
     bool disabled = false;
   };
   static constexpr int kMaxCaptureTries = 3;
-  bool use_graphs = true;
   // capturing: per host thread (the encoder thread may capture while the model thread launches eagerly)
   static thread_local bool capturing;
   bool capture_failed = false;
@@ -466,6 +448,34 @@ struct dsm_engine {
 thread_local bool dsm_engine::capturing = false;
 thread_local std::shared_lock<std::shared_mutex>* dsm_engine::api_held = nullptr;
 
+// The library's whole environment: ten DSM_* variables (include/dsm.h lists them), read once per engine by create_impl and
+// tts_create_impl after dot_mode is set.  dsm_env_int is the only getenv in csrc/; the two group counts (DSM_LM_GROUPS,
+// DSM_TTS_GROUPS) go through it where they are computed.
+static int dsm_env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+static void dsm_read_env(dsm_engine* e, bool stt) {
+  // dot_mode 1, STT engine only: the bx3 loop is cheaper per tile, so whole-K workgroups pay from 192 (n, m) tiles on (r03 sweep,
+  // profiles/r03/experiments/chunk_loop_min_mode1.txt: B = 400 13.2 -> 12.0 ms, B = 1024 27.9 -> 26.7), and the bf16 GEMMs leave
+  // the vector ALU to the attention waves, so large attention launches run three workgroups per CU (r03: 52.1 -> 50.4 ms at
+  // B = 2048, 59.8 -> 56.9 at 2304; four: 53.7).  The TTS engine has always kept 384 and 60000 in both modes (it never ran
+  // these two lines); the difference is kept on purpose: dropping it would change which kernels a TTS step launches.
+  if (stt && e->dot_mode == 1) {
+    e->chunk_loop_min_tiles = 192;
+    e->attn_lds_pad = 40000;
+  }
+  e->use_graphs = dsm_env_int("DSM_GRAPHS", 1) != 0;
+  e->fuse_qkv = dsm_env_int("DSM_FUSE_QKV", 1) != 0;
+  e->stream_prio = dsm_env_int("DSM_STREAM_PRIO", 0) != 0;  // the TTS engine's two streams have no priorities: ignored there
+  e->fuse_front = dsm_env_int("DSM_FUSE_FRONT", 0) != 0;
+  e->chunk_loop_min_tiles = dsm_env_int("DSM_CHUNK_LOOP_MIN", e->chunk_loop_min_tiles);
+  e->loop_depth = dsm_env_int("DSM_LOOP_DEPTH", 4) == 2 ? 2 : 4;
+  e->smallk_min_tiles = dsm_env_int("DSM_SMALLK_MIN", e->smallk_min_tiles);
+  const int mt = dsm_env_int("DSM_SMALLK_MT", e->smallk_mt);
+  if (mt == 1 || mt == 2 || mt == 4) e->smallk_mt = mt;
+}
+
 // shared side of dsm_engine::api_mu for the length of one API call: EVERY entry point that issues HIP work holds it (r03;
 // r02 had it on the two ticket entry points only, and the synchronous pair dsm_mimi_encode_step || dsm_asr_step_tokens of
 // tests/harness ran unprotected).  Nested entry points (one public call inside another on the same thread) share the outer hold.
@@ -542,10 +552,9 @@ int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // elements, lane q * 16 + r inside it — every weight load instruction covers eight full 128-byte lines instead of sixteen half
 // lines 4 KB apart, and a wave's chunk is 8 KB of one DRAM page run (experiments/gemm_wk_probe: QKV / gate launches -10 %).
 // split_row: a row offset the kernels address as a tile origin (the gate's up half at +hidden): must be a multiple of 16, else
-// the matrix stays row-major.  DSM_WPACK=0: row-major everywhere.
+// the matrix stays row-major.  The layout depends on the configuration alone, so every rank that attaches to an arena agrees on it.
 int pack_linear(dsm_engine* e, Linear* L, const float* w, int N, int K, bool bf16, const float* bias, int split_row = 0) {
-  static const bool wpack = !(getenv("DSM_WPACK") && atoi(getenv("DSM_WPACK")) == 0);
-  L->packed = bf16 && wpack && (split_row % 16 == 0);
+  L->packed = bf16 && (split_row % 16 == 0);
   L->N = N;
   L->K = K;
   L->Npad = round_up(N, 64) + 64;  // the tiled kernel reads whole 64-row tiles (and the gate's up-tile at +hidden)
@@ -942,77 +951,75 @@ int alloc_mimi_state(dsm_engine* e, MimiState* s, const MimiW& w, int B) {
 // ----------------------------------------------------------------------------------------------
 // GEMM launch
 // ----------------------------------------------------------------------------------------------
-// whole-K-in-the-workgroup GEMMs (dsm_gemm_wk.h): dot_mode 1, bf16 weights, at most four K-chunks (DSM_WK_GATE_CHUNKS), M <= 64
+// whole-K-in-the-workgroup GEMMs (dsm_gemm_wk.h): dot_mode 1, bf16 weights, at most four K-chunks, M <= 64
 bool wk_applicable(const dsm_engine* e, bool bf16_weights, int Kpad, int K, int M) {
   const int chunks = (Kpad + DSM_KC - 1) / DSM_KC;
-  return bf16_weights && e->dot_mode == 1 && K % 32 == 0 && Kpad == K && chunks <= e->wk_gate_max_chunks && chunks <= 4 && M <= 64;
+  return bf16_weights && e->dot_mode == 1 && K % 32 == 0 && Kpad == K && chunks <= 4 && M <= 64;
+}
+
+// The one launch of launch_gemm_tiled, for MT 16-row tiles per workgroup.
+//   dot_mode 1, bf16 weights (bx3): whole K in the workgroup -> gemm_bx3_kernel<.., true>; split-K at M <= 32 -> gemm_bx3u_kernel,
+//     which issues every load of its chunk up front (r04; 48 KB of LDS at MT = 2, 24 KB at MT = 1); split-K at MT = 4 ->
+//     gemm_bx3_kernel<.., false>
+//   otherwise: whole K (roll) -> gemm_loop_kernel with a four- or two-block load window; split-K -> gemm_tile_kernel
+template <typename WT, typename KVT, int EPI, int NT, int MT>
+void launch_tile(hipStream_t st, dim3 grid, const GemmArgs& a, bool bx3, bool roll, bool deep) {
+  constexpr int DMAX = LoopDepth<WT, NT>::MAX;
+  if (bx3 && EPI != EPI_RVQ) {
+    if (a.chunk_loop > 1) hipLaunchKernelGGL((gemm_bx3_kernel<KVT, MT, NT, EPI, true>), grid, dim3(256), 0, st, a);
+    else if constexpr (MT == 4) hipLaunchKernelGGL((gemm_bx3_kernel<KVT, 4, NT, EPI, false>), grid, dim3(256), 0, st, a);
+    else if constexpr (MT == 2) hipLaunchKernelGGL((gemm_bx3u_kernel<KVT, 2, NT, EPI, 8, 0, 4>), grid, dim3(256), 8 * 3 * 32 * 32 * 2, st, a);
+    else hipLaunchKernelGGL((gemm_bx3u_kernel<KVT, 1, NT, EPI, 8>), grid, dim3(256), 8 * 3 * 16 * 32 * 2, st, a);
+  } else if (roll && deep) hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MT, NT, EPI, DMAX>), grid, dim3(256), 0, st, a);
+  else if (roll) hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MT, NT, EPI, 2>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((gemm_tile_kernel<WT, KVT, MT, NT, EPI>), grid, dim3(256), 0, st, a);
 }
 
 template <typename WT, typename KVT, int EPI, int NT>
 int launch_gemm_tiled(dsm_engine* e, hipStream_t st, GemmArgs& a) {
   int chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
   const int gx = (a.N + 63) / 64;
-  // Enough (n, m) tiles to fill the chip (large batches; the Mimi convs, whose M is B x frames): no
+  const bool bx3 = e->dot_mode == 1 && sizeof(WT) == 2;  // dot_mode 1: every bf16-weight GEMM on the bf16 matrix pipe
+  auto ok4 = [](const RowMap& m) { return m.ld % 4 == 0 && m.bstride % 4 == 0; };
+  a.vec = (a.N % 4 == 0) && (!a.Y || ok4(a.ymap)) && (!a.Y2 || ok4(a.y2map)) && (!a.res || ok4(a.rmap));
+  // ---- chunk loop.  Enough (n, m) tiles to fill the chip (large batches; the Mimi convs, whose M is B x frames): no
   // split-K across workgroups — each walks the chunks itself and sums them in order in registers, so the slabs
   // (chunks x M x N floats written, then read back by a reduce launch) disappear.
   a.chunk_loop = 0;
-  if (chunks > 1 && e->chunk_loop && (long)gx * ((a.M + 63) / 64) >= e->chunk_loop_min_tiles) {
+  if (chunks > 1 && (long)gx * ((a.M + 63) / 64) >= e->chunk_loop_min_tiles) {
     a.chunk_loop = chunks;
     a.defer_reduce = 0;
     chunks = 1;
   }
-  // r04: short reductions (the DepFormer's: K = 1024) keep the whole K inside the workgroup — four waves, one chunk each,
-  // 16 rows x one (gate, up) tile pair (or one tile) per workgroup, the epilogue behind the ordered LDS sum: no slabs, no
-  // reduce launch.  experiments/gemm_wk_probe: gate 7.5 us against 13.4 (10.9 with gemm_bx3u_kernel) at M = 32; at K = 2048 the
-  // activation re-read (every workgroup reads 16 x K x 4 bytes from L2) makes it lose (27 against 20 us).  With
-  // a.pre_norm_w the row norm of the input runs in the kernel's prologue (gemm_wkn_kernel) and the norm launch goes too.
-  {
-    const bool wk_can = wk_applicable(e, sizeof(WT) == 2, a.Kpad, a.K, a.M) && a.chunk_loop == 0 && chunks > 1 && a.N % 16 == 0;
-    const bool wk = wk_can && ((EPI == EPI_GATE && NT == 2) ? true : (EPI == EPI_STORE && NT == 1 && a.wk_hint));
-    if (a.pre_norm_w && !(wk && EPI == EPI_GATE)) {
-      e->set_error("internal: a norm prologue was requested for a GEMM that does not run whole-K (K=%d M=%d)", a.K, a.M);
-      return DSM_ERR_STATE;
-    }
-    if (wk) {
-      auto ok4 = [](const RowMap& m) { return m.ld % 4 == 0 && m.bstride % 4 == 0; };
-      a.vec = (a.N % 4 == 0) && (!a.Y || ok4(a.ymap)) && (!a.Y2 || ok4(a.y2map)) && (!a.res || ok4(a.rmap));
+  // ---- whole-K gate.  r04: short reductions (the DepFormer's: K = 1024) keep the whole K inside the workgroup — four waves, one
+  // chunk each, 16 rows x one (gate, up) tile pair per workgroup, the epilogue behind the ordered LDS sum: no slabs, no reduce
+  // launch.  experiments/gemm_wk_probe: gate 7.5 us against 13.4 (10.9 with gemm_bx3u_kernel) at M = 32; at K = 2048 the
+  // activation re-read (every workgroup reads 16 x K x 4 bytes from L2) makes it lose (27 against 20 us).
+  if constexpr (EPI == EPI_GATE && NT == 2) {
+    if (wk_applicable(e, sizeof(WT) == 2, a.Kpad, a.K, a.M) && chunks > 1 && a.N % 16 == 0) {
       a.ts = e->timeline ? e->dev_ts_slot(e->tag_gemm[e->sid(st)], e->sid(st), 1, 2) : nullptr;
       const int ph = e->prof_begin(e->tag_gemm[e->sid(st)], st);
-      const dim3 grid(a.N / 16, 1, (a.M + 15) / 16);
-      if (EPI == EPI_GATE && a.pre_norm_w && a.pre_norm_rms)
-        hipLaunchKernelGGL((gemm_wkn_kernel<KVT, 2, EPI_GATE, true>), grid, dim3(256), (size_t)chunks * 2 * 1024 + 512 + 8192, st, a);
-      else if (EPI == EPI_GATE && a.pre_norm_w)
-        hipLaunchKernelGGL((gemm_wkn_kernel<KVT, 2, EPI_GATE, false>), grid, dim3(256), (size_t)chunks * 2 * 1024 + 512 + 8192, st, a);
-      else if (EPI == EPI_GATE)
-        hipLaunchKernelGGL((gemm_wk_kernel<KVT, 1, 2, EPI_GATE, 1, 4, 2, true, 4>), grid, dim3(256), (size_t)chunks * 2 * 1024, st, a);
-      else
-        hipLaunchKernelGGL((gemm_wk_kernel<KVT, 1, 1, EPI_STORE, 1, 4, 2, true, 4>), grid, dim3(256), (size_t)chunks * 1024, st, a);
+      hipLaunchKernelGGL((gemm_wk_kernel<KVT, 1, 2, EPI_GATE, 1, 4, 2, true, 4>), dim3(a.N / 16, 1, (a.M + 15) / 16), dim3(256),
+                         (size_t)chunks * 2 * 1024, st, a);
       e->prof_end(ph, st);
       HIPCHK(hipGetLastError());
-      if (a.norm_out) {
-        hipLaunchKernelGGL(row_norm_kernel, dim3(a.M), dim3(256), 0, st, a.norm_out, a.Y, a.norm_w, a.norm_b, a.M, a.N, a.norm_eps, a.norm_rms);
-        HIPCHK(hipGetLastError());
-      }
       return 0;
     }
   }
+  // ---- MT: 16-row tiles per workgroup
   int MT = a.M > 32 ? 4 : (a.M > 16 ? 2 : 1);
   while (MT > 1 && (long)gx * chunks * ((a.M + 16 * MT - 1) / (16 * MT)) < 256) MT /= 2;  // cover the 256 CUs
   // 33..64 rows, dot_mode 1, a launch of at most 256 workgroups (out_proj of a 2048-wide model): two 32-row z-tiles on
   // gemm_bx3u_kernel instead of one 64-row tile on gemm_bx3_kernel — 12.8 against 15.4 us with its reduce (experiments/gemm_wk_probe 3,
-  // form 5); the wider launches (QKV, gate, ff_out) tie or lose that way and keep MT = 4.  DSM_BX3U_M64=0: off.
-  if (MT == 4 && e->bx3u && e->bx3u_m64 && e->dot_mode == 1 && sizeof(WT) == 2 && chunks > 1 && a.chunk_loop == 0 && a.M <= 64 &&
-      (long)gx * chunks <= 256 && EPI == EPI_STORE)
-    MT = 2;
+  // form 5); the wider launches (QKV, gate, ff_out) tie or lose that way and keep MT = 4.
+  if (MT == 4 && bx3 && chunks > 1 && a.M <= 64 && (long)gx * chunks <= 256 && EPI == EPI_STORE) MT = 2;
   // one K-chunk and thousands of m-tiles (the first SEANet layers at large batches: K = 32..192, M = B x 1920): a
   // workgroup is one short dependent chain — loads, one to six MFMA blocks, residual load, store — so what counts is how
   // many of them a CU holds; gemm_tile_kernel's up-front window of eight blocks costs 200-230 VGPRs (two workgroups per CU),
   // gemm_loop_kernel's two-block window 150 (three).  Mimi encode alone at B = 2048: 17.7 -> 16.6 ms; 8-row tiles no better.
-  const bool smallk = e->smallk_loop && chunks == 1 && a.chunk_loop == 0 && (long)gx * ((a.M + 63) / 64) >= e->smallk_min_tiles &&
-                      !(e->dot_mode == 1 && sizeof(WT) == 2);
+  const bool smallk = chunks == 1 && a.chunk_loop == 0 && (long)gx * ((a.M + 63) / 64) >= e->smallk_min_tiles && !bx3;
   if (smallk && e->smallk_mt < MT) MT = e->smallk_mt;
-  auto ok4 = [](const RowMap& m) { return m.ld % 4 == 0 && m.bstride % 4 == 0; };
-  a.vec = (a.N % 4 == 0) && (!a.Y || ok4(a.ymap)) && (!a.Y2 || ok4(a.y2map)) && (!a.res || ok4(a.rmap));
+  // ---- split-K workspace
   a.ws_ntiles = (((NT - 1) * a.nt_stride) >> 4) + gx * 4;
   const int mtiles = (a.M + 15) / 16;
   if (chunks > 1) {
@@ -1036,12 +1043,13 @@ int launch_gemm_tiled(dsm_engine* e, hipStream_t st, GemmArgs& a) {
     }
     a.ws = e->gemm_ws[wsid];
   }
+  // ---- the launch
   dim3 grid(gx, chunks, (a.M + 16 * MT - 1) / (16 * MT));
-  // dot_mode 1, whole-K form, plain epilogues: two n-tiles per wave (128 weight rows per workgroup).  With one n-tile a wave
-  // reads 12 LDS fragments (12 KB) per block for 12 MFMAs and the LDS, not the matrix pipe, bounds the loop; the gate has
-  // always run two.  DSM_BX3_NT2=0: one.
-  const bool nt2 = NT == 1 && e->dot_mode == 1 && sizeof(WT) == 2 && e->bx3_nt2 && a.chunk_loop > 1 && MT == 4 &&
-                   (EPI == EPI_STORE || EPI == EPI_QKV) && a.N % 128 == 0 && (long)(a.N / 128) * grid.z >= e->bx3_nt2_min;
+  // dot_mode 1, whole-K form, plain epilogues, from 256 workgroups on: two n-tiles per wave (128 weight rows per workgroup).  With
+  // one n-tile a wave reads 12 LDS fragments (12 KB) per block for 12 MFMAs and the LDS, not the matrix pipe, bounds the loop; the
+  // gate has always run two.
+  const bool nt2 = NT == 1 && bx3 && a.chunk_loop > 1 && MT == 4 && (EPI == EPI_STORE || EPI == EPI_QKV) && a.N % 128 == 0 &&
+                   (long)(a.N / 128) * grid.z >= 256;
   if (nt2) {
     grid.x = a.N / 128;
     a.wg_cols = 128;
@@ -1049,32 +1057,13 @@ int launch_gemm_tiled(dsm_engine* e, hipStream_t st, GemmArgs& a) {
   }
   a.ts = e->timeline ? e->dev_ts_slot(e->tag_gemm[e->sid(st)], e->sid(st), 1, 2) : nullptr;
   const int ph = e->prof_begin(e->tag_gemm[e->sid(st)], st);
-  const bool bx3 = e->dot_mode == 1 && sizeof(WT) == 2;  // dot_mode 1: every bf16-weight GEMM on the bf16 matrix pipe
-  const bool roll = (a.chunk_loop > 1 && e->roll_prefetch) || smallk;  // whole K in the workgroup with a rolling load window
-  constexpr int DMAX = LoopDepth<WT, NT>::MAX;
-  const bool deep = DMAX == 4 && e->loop_depth == 4 && !smallk;
-  // extra dynamic LDS per GEMM workgroup (never touched): caps how many of them a CU takes, so that another stream's
-  // attention workgroups keep register file and wave slots beside them (DSM_GEMM_LDS_PAD, large launches only)
-  const size_t pad = ((long)grid.x * grid.y * grid.z >= 1024) ? e->gemm_lds_pad : 0;
-#define DSM_LAUNCH_TILED(MTv)                                                                                   \
-  if (roll && NT == 2 && MTv == 4 && e->gate_occ3)                                                              \
-    hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MTv, NT, EPI, 2, 3>), grid, dim3(256), pad, st, a);          \
-  else if (roll && deep) hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MTv, NT, EPI, DMAX>), grid, dim3(256), pad, st, a); \
-  else if (roll) hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MTv, NT, EPI, 2>), grid, dim3(256), pad, st, a);     \
-  else hipLaunchKernelGGL((gemm_tile_kernel<WT, KVT, MTv, NT, EPI>), grid, dim3(256), pad, st, a);
-  // r04: the split-K form at M <= 32 issues every load of its chunk up front (gemm_bx3u_kernel, 48 KB of LDS at MT = 2)
-#define DSM_LAUNCH_BX3(MTv)                                                                                     \
-  if (a.chunk_loop > 1) hipLaunchKernelGGL((gemm_bx3_kernel<KVT, MTv, NT, EPI, true>), grid, dim3(256), pad, st, a); \
-  else if (MTv == 2 && e->bx3u && e->bx3u_late && pad == 0) hipLaunchKernelGGL((gemm_bx3u_kernel<KVT, 2, NT, EPI, 8, 0, 4>), grid, dim3(256), 8 * 3 * 32 * 32 * 2, st, a); \
-  else if (MTv <= 2 && e->bx3u && pad == 0) hipLaunchKernelGGL((gemm_bx3u_kernel<KVT, (MTv <= 2 ? MTv : 2), NT, EPI, 8>), grid, dim3(256), 8 * 3 * 16 * (MTv <= 2 ? MTv : 2) * 32 * 2, st, a); \
-  else hipLaunchKernelGGL((gemm_bx3_kernel<KVT, MTv, NT, EPI, false>), grid, dim3(256), pad, st, a);
-  if (nt2) {
-    hipLaunchKernelGGL((gemm_bx3_kernel<KVT, 4, (NT == 1 ? 2 : NT), (EPI == EPI_GATE ? EPI_STORE : EPI), true>), grid, dim3(256), pad, st, a);
-  } else if (bx3 && EPI != EPI_RVQ) {
-    if (MT == 4) { DSM_LAUNCH_BX3(4) } else if (MT == 2) { DSM_LAUNCH_BX3(2) } else { DSM_LAUNCH_BX3(1) }
-  } else if (MT == 4) { DSM_LAUNCH_TILED(4) } else if (MT == 2) { DSM_LAUNCH_TILED(2) } else { DSM_LAUNCH_TILED(1) }
-#undef DSM_LAUNCH_BX3
-#undef DSM_LAUNCH_TILED
+  const bool roll = a.chunk_loop > 1 || smallk;  // whole K in the workgroup with a rolling load window
+  const bool deep = LoopDepth<WT, NT>::MAX == 4 && e->loop_depth == 4 && !smallk;
+  if (nt2) hipLaunchKernelGGL((gemm_bx3_kernel<KVT, 4, (NT == 1 ? 2 : NT), (EPI == EPI_GATE ? EPI_STORE : EPI), true>), grid, dim3(256), 0, st, a);
+  else if (MT == 4) launch_tile<WT, KVT, EPI, NT, 4>(st, grid, a, bx3, roll, deep);
+  else if (MT == 2) launch_tile<WT, KVT, EPI, NT, 2>(st, grid, a, bx3, roll, deep);
+  else launch_tile<WT, KVT, EPI, NT, 1>(st, grid, a, bx3, roll, deep);
+  // ---- the reduce
   const bool rows_ok = (EPI == EPI_STORE) && a.norm_out && a.vec && !a.Y2 && a.Y && a.N <= 4096 && a.ymap.bstride == 0;
   if (chunks > 1 && !((EPI == EPI_QKV || EPI == EPI_STORE) && a.defer_reduce)) {  // deferred: the consumer sums the slabs (AttnFused, LogitSrc)
     if (rows_ok) {

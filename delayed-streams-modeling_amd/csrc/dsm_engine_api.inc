@@ -5,6 +5,11 @@ namespace {
 template <typename KVT, int HD, int T>
 int launch_attn_t(dsm_engine* e, hipStream_t st, float* out, const float* q, const void* k, const void* v,
                   const uint32_t* start_pos, const uint8_t* active, int B, int H, int ctx, int d, const AttnFused& fq) {
+  // bf16 rings: eight keys per lane group and batch at head_dim 128 (126 VGPRs; 0.69 of the HBM peak alone at 32 slots, 0.88 at 1024),
+  // four below (78 VGPRs: stt-2.6b's head_dim-64 launches 39.2 against 42.8 us).  Four at head_dim 128 buys the B = 64 step 0.6 %
+  // through co-residency and costs the kernel itself 3-4 % (38.7 against 37.0 us alone): not taken.
+  // (T = 2 on a bf16 ring — no shipped configuration — spills with eight: always four; so do the f32 rings)
+  constexpr int UNR = (sizeof(KVT) == 2 && T == 1 && HD == 128) ? 8 : 4;
   size_t lds = sizeof(float) * ((size_t)T * ctx + 4 * T * HD + 16);
   // Large launches: two workgroups per CU already saturate HBM (isolated time unchanged), and the LDS padding that
   // enforces it leaves registers for the other streams' GEMM workgroups to run beside the attention instead of queueing
@@ -12,16 +17,15 @@ int launch_attn_t(dsm_engine* e, hipStream_t st, float* out, const float* q, con
   // (only when a workgroup streams enough by itself — 384 KB for stt-1b; with stt-2.6b's 96 KB per (slot, head) two
   // workgroups per CU starve HBM: +5 %)
   if ((long)B * H >= 2048 && (size_t)2 * ctx * HD * sizeof(KVT) >= (size_t)256 * 1024) lds += e->attn_lds_pad;
-  if (lds > 64 * 1024) {  // beyond the default dynamic-LDS limit (long rings, or an experiment's padding)
+  if (lds > 64 * 1024) {  // beyond the default dynamic-LDS limit (long rings, or the padding)
     static size_t allowed = 0;
     if (lds > allowed) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<KVT, HD, T, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<KVT, HD, T, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<KVT, HD, T, UNR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       allowed = lds;
     }
   }
   const int tag = e->tag_attn[e->sid(st)];
-  if (T == 1 && HD == 64 && ctx <= 32 && e->attn_small) {  // short rings (the DepFormer's): one wave per (slot, head)
+  if (T == 1 && HD == 64 && ctx <= 32) {  // short rings (the DepFormer's): one wave per (slot, head)
     const int ph = e->prof_begin(tag, st);
     hipLaunchKernelGGL((attn_small_kernel<KVT, 64>), dim3((B * H + 3) / 4), dim3(256), 0, st, out, q, reinterpret_cast<const KVT*>(k),
                        reinterpret_cast<const KVT*>(v), start_pos, active, B * H, H, ctx, d, fq);
@@ -30,17 +34,8 @@ int launch_attn_t(dsm_engine* e, hipStream_t st, float* out, const float* q, con
     return 0;
   }
   const int ph = e->prof_begin(tag, st);
-  // bf16 rings: eight keys per lane group and batch at head_dim 128 (126 VGPRs; 0.69 of the HBM peak alone at 32 slots, 0.88 at 1024),
-  // four below (78 VGPRs: stt-2.6b's head_dim-64 launches 39.2 against 42.8 us).  Four at head_dim 128 buys the B = 64 step 0.6 %
-  // through co-residency and costs the kernel itself 3-4 % (38.7 against 37.0 us alone): not taken.  DSM_ATTN_UNR=4 / 8 forces one.
-  // (T = 2 on a bf16 ring — no shipped configuration — spills with eight: always four)
-  const bool unr8 = sizeof(KVT) == 2 && T == 1 && (e->attn_unr == 8 || (e->attn_unr == 0 && HD == 128));
-  if (unr8)
-    hipLaunchKernelGGL((attn_kernel<KVT, HD, T, 8>), dim3(B * H), dim3(256), lds, st, out, q, reinterpret_cast<const KVT*>(k),
-                       reinterpret_cast<const KVT*>(v), start_pos, active, H, ctx, d, e->dev_ts_slot(tag, e->sid(st), 0), fq);
-  else
-    hipLaunchKernelGGL((attn_kernel<KVT, HD, T, 4>), dim3(B * H), dim3(256), lds, st, out, q, reinterpret_cast<const KVT*>(k),
-                       reinterpret_cast<const KVT*>(v), start_pos, active, H, ctx, d, e->dev_ts_slot(tag, e->sid(st), 0), fq);
+  hipLaunchKernelGGL((attn_kernel<KVT, HD, T, UNR>), dim3(B * H), dim3(256), lds, st, out, q, reinterpret_cast<const KVT*>(k),
+                     reinterpret_cast<const KVT*>(v), start_pos, active, H, ctx, d, e->dev_ts_slot(tag, e->sid(st), 0), fq);
   e->prof_end(ph, st);
   HIPCHK(hipGetLastError());
   return 0;
@@ -56,29 +51,6 @@ int launch_attn(dsm_engine* e, hipStream_t st, float* out, const float* q, const
 #undef DSM_ATTN
   e->set_error("unsupported attention shape head_dim=%d T=%d (head_dim must be 32, 64 or 128; T 1 or 2)", hd, T);
   return DSM_ERR_INVALID;
-}
-
-// Experiment (DSM_ENC_CUS = n, DSM_LM_CUS_EXCL): the encoder stream on n CUs of every XCD, the LM streams on the others.
-// Mimi's GEMMs run on the f32 matrix instruction, which holds the vector ALU of its SIMD (experiments/fused_roles_probe):
-// LM attention waves that share a SIMD with them starve.  The queue's CU mask is spread over the XCDs bit by bit (bit b ->
-// XCD b % 8, CU b / 8 of it).  kind 1: encoder, 2: LM.
-int make_stream(dsm_engine* e, hipStream_t* st, int prio, int kind) {
-  const int n = e->enc_cus;
-  if (n <= 0 || n >= 32 || (kind == 2 && !e->lm_cus_excl)) {
-    HIPCHK(hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio));
-    return 0;
-  }
-  uint32_t mask[8];
-  for (int w = 0; w < 8; ++w) {
-    uint32_t m = 0;
-    for (int b = 0; b < 32; ++b) {
-      const int cu = (32 * w + b) / 8;  // CU index within its XCD
-      if ((kind == 1) == (cu < n)) m |= 1u << b;
-    }
-    mask[w] = m;
-  }
-  HIPCHK(hipExtStreamCreateWithCUMask(st, 8, mask));
-  return 0;
 }
 
 int run_norm(dsm_engine* e, hipStream_t st, float* y, const float* x, const float* w, const float* b, int rows, int d,
@@ -118,7 +90,7 @@ int transformer_forward(dsm_engine* e, hipStream_t st, const TransformerW& w, Tr
     // larger than the Infinity Cache, so they should not evict the weights the other stream group reads next.  Measured:
     // LM attention 1410 -> 1336 us/step at B = 64 (38.0 -> 36.7 us per launch alone), 31.4 -> 29.3 ms at B = 2048 (6.9 TB/s),
     // stt-2.6b 4704 -> 4560 us; the f32 rings of Mimi (T = 2) get 6-13 % SLOWER with it and keep ordinary loads.
-    fq.nt = (e->attn_nt == 2 || (e->attn_nt == 1 && sizeof(KVT) == 2)) ? 1 : 0;
+    fq.nt = sizeof(KVT) == 2;
     if (!(phase == 2 && l == 0)) {
       GemmArgs a = base_args(L.in_proj, xn, plain_map(M, d), M);
       a.Y = q;
@@ -143,19 +115,12 @@ int transformer_forward(dsm_engine* e, hipStream_t st, const TransformerW& w, Tr
     if (!(phase == 2 && l == 0))
       if (int rc = launch_attn<KVT>(e, st, att, q, s.k[l], s.v[l], s.start_pos, d_mask, B, H, hd, T, c.context, d, fq)) return rc;
     if (phase == 1) return 0;
-    // r04: where the MLP input GEMM runs whole-K-in-the-workgroup (short reductions: the DepFormer), norm2 moves into its
-    // prologue and out_proj stores the residual stream itself — out_proj, reduce + norm, gate, gate-reduce become two launches
-    const bool mid_fused = !ca && c.gating && T == 1 && e->wk_norm && wk_applicable(e, sizeof(WT) == 2, L.ff_in.Kpad, L.ff_in.K, M) &&
-                           L.ff_in.Kpad > DSM_KC && L.ff_in.K == d && wk_applicable(e, sizeof(WT) == 2, L.out_proj.Kpad, L.out_proj.K, M) &&
-                           L.out_proj.Kpad > DSM_KC && d % 16 == 0 && w.hidden % 16 == 0;
     {
       GemmArgs a = base_args(L.out_proj, att, plain_map(M, d), M);
       a.scale = L.ls1;
       a.res = x; a.rmap = plain_map(M, d);
       a.Y = x; a.ymap = plain_map(M, d);
-      if (mid_fused) {
-        a.wk_hint = 1;
-      } else if (ca) {  // norm_cross follows instead of norm2 — core/transformer.rs:755-757
+      if (ca) {  // norm_cross follows instead of norm2 — core/transformer.rs:755-757
         a.norm_w = L.ncw; a.norm_b = L.ncb; a.norm_out = xn; a.norm_eps = w.ca_norm_rms ? 1e-8f : 1e-5f; a.norm_rms = w.ca_norm_rms;
       } else {
         a.norm_w = L.n2w; a.norm_b = L.n2b; a.norm_out = xn; a.norm_eps = eps; a.norm_rms = c.norm;  // norm2
@@ -189,11 +154,10 @@ int transformer_forward(dsm_engine* e, hipStream_t st, const TransformerW& w, Tr
       if (int rc = gemm_store<WT>(e, st, a)) return rc;
     }
     if (c.gating) {  // Mlp::Gating — core/batched_transformer.rs:170-176
-      GemmArgs a = base_args(L.ff_in, mid_fused ? x : xn, plain_map(M, d), M);
+      GemmArgs a = base_args(L.ff_in, xn, plain_map(M, d), M);
       a.N = w.hidden;
       a.nt_stride = w.hidden;
       a.Y = ff; a.ymap = plain_map(M, w.hidden);
-      if (mid_fused) { a.pre_norm_w = L.n2w; a.pre_norm_b = L.n2b; a.pre_norm_eps = eps; a.pre_norm_rms = c.norm; }
       if (int rc = launch_gemm_t<WT, KVT, EPI_GATE, 2>(e, st, a, true)) return rc;
     } else {  // Mlp::NoGating — :169
       GemmArgs a = base_args(L.ff_in, xn, plain_map(M, d), M);
@@ -586,7 +550,7 @@ int lm_step(dsm_engine* e, hipStream_t st, const uint32_t* d_codes, const uint8_
   // ordinary stream event; the rest replays as a graph.  The delay costs each later group one QKV + attention per step.
   // Measured (experiments/large_batch_sweep.py, r02): -4 % per step at B = 1024, -3 % at 2048, -2 % at 512, nothing at
   // 400, +3 % at 64 (there the delay is not repaid): on from 256 slots per group.
-  const bool stagger = G > 1 && e->stagger && !e->serialize_groups && (e->stagger_force || e->lm.groups[0].nb >= 256);
+  const bool stagger = G > 1 && !e->serialize_groups && e->lm.groups[0].nb >= 256;
   for (size_t g = 0; g < G; ++g) {
     hipStream_t gs = (g == 0 || e->serialize_groups) ? st : e->s_grp[g];
     if (stagger && g > 0) HIPCHK(hipStreamWaitEvent(gs, e->ev_stagger[g - 1], 0));
@@ -881,45 +845,14 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
     return DSM_ERR_DEVICE;
   }
   HIPCHK(hipSetDevice(device_id));
+  dsm_read_env(e, true);
   // Stream priorities (DSM_STREAM_PRIO=1: LM streams high, encoder stream low) are off by default: measured +0.5 % at
   // B = 64 but -2.6 % at B = 400, where the encoder's share of the step is large and starving it delays the next frame.
   int prio_lo = 0, prio_hi = 0;
-  if (const char* env = getenv("DSM_STREAM_PRIO")) if (atoi(env) != 0) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  if (e->stream_prio) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
   e->prio_hi = prio_hi;
-  if (const char* env = getenv("DSM_FUSE_QKV")) e->fuse_qkv = atoi(env) != 0;
-  if (const char* env = getenv("DSM_GRAPHS")) e->use_graphs = atoi(env) != 0;
-  if (const char* env = getenv("DSM_STAGGER")) { e->stagger = atoi(env) != 0; e->stagger_force = atoi(env) > 1; }
-  if (const char* env = getenv("DSM_CHUNK_LOOP")) e->chunk_loop = atoi(env) != 0;
-  if (const char* env = getenv("DSM_ROLL")) e->roll_prefetch = atoi(env) != 0;
-  if (const char* env = getenv("DSM_LOOP_DEPTH")) e->loop_depth = atoi(env) == 2 ? 2 : 4;
-  if (const char* env = getenv("DSM_GATE_OCC3")) e->gate_occ3 = atoi(env) != 0;
-  if (const char* env = getenv("DSM_GEMM_LDS_PAD")) e->gemm_lds_pad = (size_t)atol(env);
-  // whole-K workgroups from this many (n, m) tiles on: 384 for the f32 instruction (r02); the bx3 loop is cheaper per tile and
-  // pays earlier (r03 sweep, profiles/r03/experiments/chunk_loop_min_mode1.txt: B = 400 13.2 -> 12.0 ms, B = 1024 27.9 -> 26.7)
-  if (c.dot_mode == 1) e->chunk_loop_min_tiles = 192;
-  if (const char* env = getenv("DSM_CHUNK_LOOP_MIN")) e->chunk_loop_min_tiles = atoi(env);
-  if (const char* env = getenv("DSM_BX3U")) e->bx3u = atoi(env) != 0;
-  if (const char* env = getenv("DSM_BX3U_M64")) e->bx3u_m64 = atoi(env) != 0;
-  if (const char* env = getenv("DSM_BX3U_LATE")) e->bx3u_late = atoi(env) != 0;
-  if (const char* env = getenv("DSM_ATTN_UNR")) e->attn_unr = atoi(env);
-  if (const char* env = getenv("DSM_ATTN_SMALL")) e->attn_small = atoi(env) != 0;
-  if (const char* env = getenv("DSM_WK_NORM")) e->wk_norm = atoi(env) != 0;
-  if (const char* env = getenv("DSM_WK_GATE_CHUNKS")) e->wk_gate_max_chunks = atoi(env);
-  if (const char* env = getenv("DSM_FUSE_FRONT")) e->fuse_front = atoi(env) != 0;
-  if (const char* env = getenv("DSM_ATTN_NT")) e->attn_nt = atoi(env);
-  if (const char* env = getenv("DSM_SMALLK_LOOP")) e->smallk_loop = atoi(env);
-  if (const char* env = getenv("DSM_SMALLK_MIN")) e->smallk_min_tiles = atoi(env);
-  if (const char* env = getenv("DSM_SMALLK_MT")) { const int v = atoi(env); if (v == 1 || v == 2 || v == 4) e->smallk_mt = v; }
-  // large attention launches: two workgroups per CU beside f32-MFMA GEMMs (r02), three beside the bf16 ones of dot_mode 1, which
-  // leave the vector ALU to the attention waves (r03: 52.1 -> 50.4 ms at B = 2048, 59.8 -> 56.9 at 2304; four: 53.7)
-  if (c.dot_mode == 1) e->attn_lds_pad = 40000;
-  if (const char* env = getenv("DSM_ATTN_LDS_PAD")) e->attn_lds_pad = (size_t)atol(env);
-  if (const char* env = getenv("DSM_ENC_CUS")) e->enc_cus = atoi(env);
-  if (const char* env = getenv("DSM_BX3_NT2")) e->bx3_nt2 = atoi(env) != 0;
-  if (const char* env = getenv("DSM_BX3_NT2_MIN")) e->bx3_nt2_min = atoi(env);
-  if (const char* env = getenv("DSM_LM_CUS_EXCL")) e->lm_cus_excl = atoi(env) != 0;
-  if (int rc = make_stream(e, &e->s_enc, prio_lo, 1)) return rc;
-  if (int rc = make_stream(e, &e->s_model, prio_hi, 2)) return rc;
+  HIPCHK(hipStreamCreateWithPriority(&e->s_enc, hipStreamNonBlocking, prio_lo));
+  HIPCHK(hipStreamCreateWithPriority(&e->s_model, hipStreamNonBlocking, prio_hi));
   HIPCHK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&e->ev_codes_consumed, hipEventDisableTiming));
   HIPCHK(hipEventCreate(&e->ev_a));
@@ -1007,8 +940,7 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
   {
     // stream groups (see LmState::Group).  Default: two groups once each still fills 16-row MFMA tiles twice over;
     // DSM_LM_GROUPS overrides (1..4) for experiments.
-    int G = B >= 32 ? 2 : 1;
-    if (const char* env = getenv("DSM_LM_GROUPS")) G = atoi(env);
+    int G = dsm_env_int("DSM_LM_GROUPS", B >= 32 ? 2 : 1);
     if (G < 1) G = 1;
     if (G > dsm_engine::kMaxGroups) G = dsm_engine::kMaxGroups;
     const int n16 = (B + 15) / 16;
@@ -1035,7 +967,7 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
       grp.view.rope_cs = s.tr.rope_cs + (size_t)b0 * hd;
       b0 += nb;
       if (g > 0) {
-        if (int rc = make_stream(e, &e->s_grp[g], e->prio_hi, 2)) return rc;
+        HIPCHK(hipStreamCreateWithPriority(&e->s_grp[g], hipStreamNonBlocking, e->prio_hi));
         HIPCHK(hipEventCreateWithFlags(&e->ev_grp_in[g], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&e->ev_grp_done[g], hipEventDisableTiming));
       }

@@ -112,18 +112,7 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
     return DSM_ERR_DEVICE;
   }
   HIPCHK(hipSetDevice(device_id));
-  if (const char* env = getenv("DSM_FUSE_QKV")) e->fuse_qkv = atoi(env) != 0;
-  if (const char* env = getenv("DSM_GRAPHS")) e->use_graphs = atoi(env) != 0;
-  if (const char* env = getenv("DSM_BX3_NT2")) e->bx3_nt2 = atoi(env) != 0;
-  if (const char* env = getenv("DSM_CHUNK_LOOP_MIN")) e->chunk_loop_min_tiles = atoi(env);
-  if (const char* env = getenv("DSM_BX3U")) e->bx3u = atoi(env) != 0;
-  if (const char* env = getenv("DSM_BX3U_M64")) e->bx3u_m64 = atoi(env) != 0;
-  if (const char* env = getenv("DSM_BX3U_LATE")) e->bx3u_late = atoi(env) != 0;
-  if (const char* env = getenv("DSM_ATTN_UNR")) e->attn_unr = atoi(env);
-  if (const char* env = getenv("DSM_ATTN_SMALL")) e->attn_small = atoi(env) != 0;
-  if (const char* env = getenv("DSM_WK_NORM")) e->wk_norm = atoi(env) != 0;
-  if (const char* env = getenv("DSM_WK_GATE_CHUNKS")) e->wk_gate_max_chunks = atoi(env);
-  if (const char* env = getenv("DSM_BX3_NT2_MIN")) e->bx3_nt2_min = atoi(env);
+  dsm_read_env(e, false);
   HIPCHK(hipStreamCreateWithFlags(&e->s_enc, hipStreamNonBlocking));
   HIPCHK(hipStreamCreateWithFlags(&e->s_model, hipStreamNonBlocking));
   hipStream_t st = e->s_model;
@@ -335,7 +324,7 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
     // 8.40 / 9.27 ms per step (three or four run as two rounds: 17.9 / 19.2 ms — the runtime kept two graphs in flight at a
     // time).  Default: one group below 96 slots, two from there on.
     int Gn = B >= 96 ? 2 : 1;  // measured (v202501, dot_mode 1): B = 32 8.4 vs 9.3 ms, 64 9.4 vs 10.1, 128 12.4 vs 11.7 (one vs two groups)
-    if (const char* env = getenv("DSM_TTS_GROUPS")) Gn = atoi(env);
+    Gn = dsm_env_int("DSM_TTS_GROUPS", Gn);
     if (Gn < 1) Gn = 1;
     if (Gn > dsm_engine::kMaxGroups) Gn = dsm_engine::kMaxGroups;
     if (Gn > B) Gn = B;

@@ -14,17 +14,12 @@ dev = torch.device("cuda", 0)
 Bs = [int(x) for x in sys.argv[1:]] or [512, 2048]
 KNOBS = [
     {},                                            # defaults: rolling window depth 4, 2 groups, graphs, staggered start from 256 slots per group
-    {"DSM_STAGGER": "0"},
     {"DSM_LM_GROUPS": "4"},
-    {"DSM_ATTN_LDS_PAD": "45000"},                 # three attention workgroups per CU instead of two
-    {"DSM_ATTN_LDS_PAD": "0"},
     {"DSM_FUSE_FRONT": "0"},
-    {"DSM_SMALLK_LOOP": "0"},
-    {"DSM_ROLL": "0"},
 ]
 for B in Bs:
     for kn in KNOBS:
-        for k in ("DSM_ROLL", "DSM_LOOP_DEPTH", "DSM_LM_GROUPS", "DSM_GRAPHS", "DSM_ATTN_LDS_PAD", "DSM_GATE_OCC3", "DSM_STAGGER", "DSM_GEMM_LDS_PAD"):
+        for k in ("DSM_LOOP_DEPTH", "DSM_LM_GROUPS", "DSM_GRAPHS", "DSM_FUSE_FRONT"):
             os.environ.pop(k, None)
         os.environ.update(kn)
         try:

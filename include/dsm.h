@@ -18,6 +18,25 @@
  *   - threading: like the reference, dsm_mimi_encode_step may run on an "encoder" thread
  *     while dsm_asr_step_tokens / dsm_asr_reset_slot run on a "model" thread
  *     (srv/batched_asr.rs:314-522); the two sides use separate HIP streams and state.
+ *
+ * Environment
+ *   The library reads exactly ten variables, once per engine at create (dsm_read_env, csrc/dsm_engine.hip).  Every value
+ *   gives the same bits; they choose among launch sequences.  STT = dsm_asr_create*, TTS = dsm_tts_create.
+ *   deployment switches
+ *     DSM_GRAPHS          1     0: every launch sequence is enqueued kernel by kernel instead of replayed as a hipGraph
+ *     DSM_LM_GROUPS       2 from 32 slots, else 1   STT: stream groups of the LM step (1..4)
+ *     DSM_TTS_GROUPS      2 from 96 slots, else 1   TTS: stream groups of the step (1..4)
+ *     DSM_FUSE_QKV        1     0: a split-K QKV (or cross-attention query) GEMM keeps its own reduce launch instead of
+ *                               leaving the slabs to the attention kernel's prologue
+ *     DSM_STREAM_PRIO     0     1: STT: LM streams at high, encoder stream at low priority (TTS: ignored, its streams
+ *                               have no priorities)
+ *   test levers (they push the large-batch kernels through small shapes; not for deployments)
+ *     DSM_CHUNK_LOOP_MIN  384; STT in dot_mode 1: 192   whole-K-in-the-workgroup GEMMs from this many 64 x 64 tiles on
+ *     DSM_LOOP_DEPTH      4     2: those GEMMs' rolling load window holds two blocks instead of four
+ *     DSM_SMALLK_MIN      1024  one-chunk GEMMs (K <= 256) run on the loop kernel from this many 64-row tiles on
+ *     DSM_SMALLK_MT       4     16-row tiles per workgroup of those launches (1, 2 or 4)
+ *     DSM_FUSE_FRONT      0     1: the SEANet front end as one fused kernel (not bit-reproducible beside dot_mode 1 LM
+ *                               kernels on the same CUs: DESIGN.md section 8)
  */
 #ifndef DSM_H
 #define DSM_H

@@ -53,21 +53,20 @@ def test_the_two_modes_differ_in_bits_not_in_value(gpu, dsm, lib, tiny_weights):
     e0.close(); e1.close()
 
 
+# (explicit ids: the four cases keep the ids under which their results have been recorded so far)
 @pytest.mark.parametrize("name,kw,frames", [
-    ("bf16_hd128_ctx300", dict(lm_heads=4, lm_head_dim=128, lm_context=300, kv_bf16=1), 40),
-    ("f32_hd64_ctx300", dict(lm_heads=8, lm_head_dim=64, lm_context=300, kv_bf16=0, mimi_head_dim=32, mimi_context=600), 24),
+    pytest.param("bf16_hd128_ctx300", dict(lm_heads=4, lm_head_dim=128, lm_context=300, kv_bf16=1), 40, id="0-bf16_hd128_ctx300-kw0-40"),
+    pytest.param("f32_hd64_ctx300", dict(lm_heads=8, lm_head_dim=64, lm_context=300, kv_bf16=0, mimi_head_dim=32, mimi_context=600), 24,
+                 id="0-f32_hd64_ctx300-kw1-24"),
     # rings of at most 32 positions with head_dim 64: attn_small_kernel (one wave per (slot, head)) with the fused QKV prologue,
     # RoPE and ring wrap after 24 frames, on the bf16 and on the f32 ring
-    ("bf16_hd64_ctx24", dict(lm_heads=8, lm_head_dim=64, lm_context=24, kv_bf16=1), 40),
-    ("f32_hd64_ctx32", dict(lm_heads=8, lm_head_dim=64, lm_context=32, kv_bf16=0), 40),
+    pytest.param("bf16_hd64_ctx24", dict(lm_heads=8, lm_head_dim=64, lm_context=24, kv_bf16=1), 40, id="0-bf16_hd64_ctx24-kw2-40"),
+    pytest.param("f32_hd64_ctx32", dict(lm_heads=8, lm_head_dim=64, lm_context=32, kv_bf16=0), 40, id="0-f32_hd64_ctx32-kw3-40"),
 ])
-@pytest.mark.parametrize("wk_norm", ["0", "1"])
-def test_medium_two_chunk_models_bx3(gpu, dsm, lib, orc, name, kw, frames, wk_norm, monkeypatch):
+def test_medium_two_chunk_models_bx3(gpu, dsm, lib, orc, name, kw, frames):
     """d_model 512 = two K-chunks: split-K slabs through gemm_bx3u_kernel + the attention prologue's ordered reduce, and the
-    whole-K forms (r04): the gate through gemm_wk_kernel; with DSM_WK_NORM=1 also out_proj whole-K with the residual in its epilogue
-    and norm2 in the gate's prologue (gemm_wkn_kernel: waves 2 and 3 own no chunk and contribute +0 totals)."""
+    whole-K form (r04): the gate through gemm_wk_kernel (waves 2 and 3 own no chunk and contribute +0 totals)."""
     from dsm_amd import synth
-    monkeypatch.setenv("DSM_WK_NORM", wk_norm)
     cfg = dsm.config_medium(**kw)
     cfg.dot_mode = 1
     lm, mimi = synth.make_synth_weights(cfg, WEIGHTS_DIR, tag="medium_" + name)
@@ -89,7 +88,7 @@ def test_stt_1b_real_dimensions_bx3(gpu, dsm, lib, orc):
 @pytest.mark.parametrize("B", [64, 128, 1024])
 def test_real_dimensions_large_batches_by_slot_independence_bx3(gpu, dsm, lib, B):
     """B = 64: two stream groups of 32 (MT = 2, split-K slabs, fused QKV prologue); B = 128: groups of 64 rows — one 64-row tile on
-    gemm_bx3_kernel for QKV / gate / ff_out, two 32-row z-tiles on gemm_bx3u_kernel for out_proj (DSM_BX3U_M64); B = 1024: gemm_bx3_kernel's whole-K loop
+    gemm_bx3_kernel for QKV / gate / ff_out, two 32-row z-tiles on gemm_bx3u_kernel for out_proj; B = 1024: gemm_bx3_kernel's whole-K loop
     form over 8 m-tiles per group.  Streams never interact: every slot must equal, bit for bit, the same stream stepped by the
     B = 4 engine that test_stt_1b_real_dimensions_bx3 ties to the oracle."""
     from dsm_amd import synth

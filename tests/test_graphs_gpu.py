@@ -42,7 +42,7 @@ def test_graph_replay_equals_eager_asr(gpu, dsm, lib, tiny_weights, monkeypatch)
     eager, (g0, e0) = _run_asr(dsm, cfg, B, *tiny_weights, steps, masks, resets, pcm)
     monkeypatch.delenv("DSM_GRAPHS")
     graph, (g1, e1) = _run_asr(dsm, cfg, B, *tiny_weights, steps, masks, resets, pcm)
-    groups = int(os.environ.get("DSM_LM_GROUPS", "2"))  # tools/knob_parity_sweep.sh runs this file with one group too
+    groups = int(os.environ.get("DSM_LM_GROUPS", "2"))  # this file may be run with one group too
     assert g0 == 0 and e0 == (2 + groups) * steps  # encode, decode and the LM groups of a step, all eager
     # two settling runs per sequence, plus a re-settle whenever a split-K workspace still grew (first decode call): then replay
     n = 2 + groups

@@ -77,7 +77,6 @@ python3 tools/trace_summary.py $P/trace_26b 14 > $P/kernel_trace_stt_2.6b_summar
 unset DSM_GRAPHS
 step tl2048 300 bash -c "python tools/timeline.py 2048 2 > $X/timeline_b2048.txt 2>&1"
 step tl64 200 bash -c "python tools/timeline.py 64 2 > $X/timeline_b64.txt 2>&1"
-step sweep 400 bash -c "tools/knob_sweep_b64.sh > $X/knob_sweep_b64.txt 2>&1"
 fi
 python3 tools/trace_summary.py $P/trace_1stream 14 2>/dev/null
 ls $P $P/extra

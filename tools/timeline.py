@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device-side timeline of one step of the two-stream pipeline (encoder stream + LM group streams), from in-kernel
 wall-clock brackets (dsm_prof_timeline): which launches really run beside which.  rocprofv3's tracing serialises the
-queues, so it cannot show this.   python tools/timeline.py [B] [steps]  (DSM_STAGGER / DSM_LM_GROUPS as usual)"""
+queues, so it cannot show this.   python tools/timeline.py [B] [steps]  (DSM_LM_GROUPS as usual)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,7 +35,7 @@ recs = sorted(eng.prof_timeline_read(), key=lambda r: r[3])
 eng.prof_enable([])
 kinds = {0: "attn", 1: "gemm", 2: "reduce"}
 span = max(r[4] for r in recs) - min(r[3] for r in recs)
-print(f"B={B} steps={steps} groups={eng.stream_groups()} stagger={os.environ.get('DSM_STAGGER', '1')}: {len(recs)} bracketed launches over {span:.0f} us "
+print(f"B={B} steps={steps} groups={eng.stream_groups()}: {len(recs)} bracketed launches over {span:.0f} us "
       f"({span / steps:.0f} us/step; profiling brackets force eager launches)")
 sids = sorted({r[0] for r in recs})
 busy = {s: sum(r[4] - r[3] for r in recs if r[0] == s) for s in sids}
