@@ -132,7 +132,7 @@ ABI_SYMBOLS = [
     "dsm_mimi_encode_step_async", "dsm_asr_step_tokens_ticket", "dsm_worker_recv", "dsm_worker_buffered",
     "dsm_tts_config_v202501", "dsm_tts_create", "dsm_tts_destroy", "dsm_tts_last_error", "dsm_tts_step",
     "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot", "dsm_tts_debug_read", "dsm_tts_get_metrics", "dsm_tts_set_sampling",
-    "dsm_tts_set_ca_src",
+    "dsm_tts_set_ca_src", "dsm_tts_attach_mimi", "dsm_tts_step_pcm", "dsm_tts_recv_pcm", "dsm_tts_pcm_pending",
 ]
 PROF_TAGS = ["attn_lm", "gemm_lm", "attn_mimi", "gemm_mimi", "rvq", "other"]
 
@@ -266,6 +266,10 @@ def load_library(path=None):
     lib.dsm_tts_get_metrics.argtypes = [vp, C.POINTER(Metrics)]
     lib.dsm_tts_set_sampling.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_uint64]
     lib.dsm_tts_set_ca_src.argtypes = [vp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_double]
+    lib.dsm_tts_attach_mimi.argtypes = [vp, C.POINTER(MimiConfig), C.c_char_p]
+    lib.dsm_tts_step_pcm.argtypes = [vp, vp, vp, vp, vp, vp, fp, u8p]
+    lib.dsm_tts_recv_pcm.argtypes = [vp, fp, u8p]
+    lib.dsm_tts_pcm_pending.argtypes = [vp]
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
         getattr(lib, name).restype = C.c_int
@@ -889,6 +893,35 @@ class TtsEngine:
         audio = np.zeros((self.B, self.S), dtype=np.uint32)
         self._check(self.lib.dsm_tts_step(self.h, _ptr(prev), _ptr(allowed), _ptr(mask), _ptr(text), _ptr(audio)))
         return text, audio
+
+    def attach_mimi(self, mimi_cfg, path):
+        """The Mimi that decodes the generated frames (srv/tts.rs:309-310); needs n_q == dep_num_slices."""
+        self._check(self.lib.dsm_tts_attach_mimi(self.h, C.byref(mimi_cfg), path.encode()))
+
+    def step_pcm(self, prev_text_token, allowed, mask, defer=False):
+        """step() + the decode of the frame the step completed.  Returns (text, audio, pcm [B][1920], valid [B]); with
+        defer=True only (text, audio): the decode is enqueued and its result comes out of recv_pcm(), in order."""
+        prev = np.ascontiguousarray(prev_text_token, dtype=np.uint32).reshape(self.B)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32).reshape(self.B)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        text = np.zeros(self.B, dtype=np.uint32)
+        audio = np.zeros((self.B, self.S), dtype=np.uint32)
+        pcm = None if defer else np.zeros((self.B, FRAME_SIZE), dtype=np.float32)
+        valid = None if defer else np.zeros(self.B, dtype=np.uint8)
+        self._check(self.lib.dsm_tts_step_pcm(self.h, _ptr(prev), _ptr(allowed), _ptr(mask), _ptr(text), _ptr(audio),
+                                              _ptr(pcm), _ptr(valid)))
+        return (text, audio) if defer else (text, audio, pcm, valid)
+
+    def recv_pcm(self):
+        """The oldest deferred step's (pcm, valid), or None when nothing is pending."""
+        pcm = np.zeros((self.B, FRAME_SIZE), dtype=np.float32)
+        valid = np.zeros(self.B, dtype=np.uint8)
+        if self._check(self.lib.dsm_tts_recv_pcm(self.h, _ptr(pcm), _ptr(valid))) == 0:
+            return None
+        return pcm, valid
+
+    def pcm_pending(self):
+        return self._check(self.lib.dsm_tts_pcm_pending(self.h))
 
     def audio_tokens(self, slot, step):
         out = np.zeros(self.S, dtype=np.uint32)

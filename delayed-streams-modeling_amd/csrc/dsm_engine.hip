@@ -151,6 +151,9 @@ struct MimiDecState {  // Mimi::decode_step state, allocated on first use
   bool ready = false, first_call = true;
   uint32_t* codes = nullptr;
   uint8_t* mask = nullptr;
+  // [B], TTS decode path only (dsm_tts_attach_mimi): a slot behaves as a fresh module of its own — the carry terms follow this
+  // flag instead of first_call (null: module-level first call, Mimi::decode_step of one batched module)
+  uint8_t* started = nullptr;
   float *q_first = nullptr, *q_rest = nullptr, *emb = nullptr, *up_carry = nullptr;
   float *x_tr = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *ff = nullptr;
   TransformerState tr;

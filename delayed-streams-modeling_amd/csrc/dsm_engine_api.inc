@@ -289,7 +289,7 @@ int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
   // carried conv state: masked in-place shift of every concat buffer (core/conv.rs:347-367)
   if (!s.h_descs.empty()) {
     hipLaunchKernelGGL(conv_state_shift_kernel, dim3(B, (unsigned)s.h_descs.size()), dim3(256), 0, st, s.descs, s.mask,
-                       s.first_call ? 1 : 0);
+                       s.first_call ? 1 : 0, nullptr);
     HIPCHK(hipGetLastError());
   }
   s.first_call = false;
@@ -383,7 +383,7 @@ int mimi_decode_body(dsm_engine* e, hipStream_t st) {
   }
   // ConvTrUpsample1d::step — core/conv.rs:603-605
   hipLaunchKernelGGL(upsample_dw_kernel, dim3(B), dim3(256), 0, st, s.emb, w.upsample_w, s.up_carry, s.x_tr, s.mask, dim,
-                     c.downsample_stride, 2 * c.downsample_stride, s.first_call ? 0 : 1);
+                     c.downsample_stride, 2 * c.downsample_stride, s.first_call ? 0 : 1, s.started);
   HIPCHK(hipGetLastError());
   // decoder_transformer.step; its output lands in the decoder's first conv buffer
   if (int rc = transformer_forward<float, float>(e, st, w.dec_tr, s.tr, s.x_tr, s.xn, s.q, s.att, s.ff, B, T2, s.mask,
@@ -406,6 +406,7 @@ int mimi_decode_body(dsm_engine* e, hipStream_t st) {
       o.T = sw.T_in; o.s = sw.stride; o.OC = sw.out_c; o.has_state = s.first_call ? 0 : 1;
       o.Y = ss.y; o.ymap = plain_map(B * T_out, sw.out_c);
       o.Y2 = ss.cat_ra; o.y2map = cat_map(sw.ra);
+      o.started = s.started;
       const int per_b = T_out * (sw.out_c / 4);
       hipLaunchKernelGGL(convtr_overlap_add_kernel, dim3((per_b + 255) / 256 < 64 ? (per_b + 255) / 256 : 64, B), dim3(256), 0,
                          st, o);
@@ -427,7 +428,7 @@ int mimi_decode_body(dsm_engine* e, hipStream_t st) {
     return rc;
   if (!s.h_descs.empty()) {
     hipLaunchKernelGGL(conv_state_shift_kernel, dim3(B, (unsigned)s.h_descs.size()), dim3(256), 0, st, s.descs, s.mask,
-                       s.first_call ? 1 : 0);
+                       s.first_call ? 1 : 0, s.started);
     HIPCHK(hipGetLastError());
   }
   s.first_call = false;

@@ -2124,8 +2124,11 @@ struct ConvStateDesc {
   int S, T, C, replicate;
 };
 
+// started (optional, [B]): per-slot freshness instead of the module-level first call (the TTS decode path): the states of
+// a slot that has not started are zero already (allocation, slot reset), and this launch — the last one of a decode step, behind
+// every reader of the flag — records that an active slot has started.
 __global__ void conv_state_shift_kernel(const ConvStateDesc* __restrict__ descs, const uint8_t* __restrict__ active,
-                                        int first_call) {
+                                        int first_call, uint8_t* __restrict__ started) {
   const ConvStateDesc dsc = descs[blockIdx.y];
   const int b = blockIdx.x;
   float* base = dsc.cat + (long)b * dsc.bstride;
@@ -2134,7 +2137,8 @@ __global__ void conv_state_shift_kernel(const ConvStateDesc* __restrict__ descs,
     const float* src = base + (long)dsc.T * dsc.C;
     // S <= T for every conv of the model, so source and destination do not overlap
     for (int i = threadIdx.x; i < n; i += blockDim.x) base[i] = src[i];
-  } else if (first_call) {
+    if (started && blockIdx.y == 0 && threadIdx.x == 0) started[b] = 1;
+  } else if (first_call && !started) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) base[i] = 0.0f;
   }
 }
@@ -2217,10 +2221,12 @@ __global__ void rvq_gather_sum_kernel(RvqGatherArgs a, const uint32_t* __restric
 
 // ConvTrUpsample1d::step — depthwise ConvTranspose1d k = 2*stride, one input frame per step, no bias
 // (core/conv.rs:558-606, :448-501).  x [B][C]; w [k][C]; carry [B][k - s][C]; y [B][s][C].
+// started (optional, [B]): the carry term is applied iff the SLOT has decoded a frame before (has_state is ignored).
 __global__ void upsample_dw_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ carry,
                                    float* __restrict__ y, const uint8_t* __restrict__ active, int C, int s, int k,
-                                   int has_state) {
+                                   int has_state, const uint8_t* __restrict__ started) {
   const int b = blockIdx.x;
+  if (started) has_state = started[b];  // a slot that has not started keeps the zero carry of its allocation / reset
   for (int i = threadIdx.x; i < s * C; i += blockDim.x) {
     const int o = i / C, c = i % C;
     const float xv = x[(long)b * C + c];
@@ -2251,9 +2257,11 @@ struct OverlapAddArgs {
   RowMap ymap;  // rows are (b, o), rpb = T*s
   float* Y2;
   RowMap y2map;
+  const uint8_t* started;  // optional [B]: the carry term is applied iff the SLOT has decoded a frame before (has_state is ignored)
 };
 __global__ void convtr_overlap_add_kernel(OverlapAddArgs a) {
   const int b = blockIdx.y;
+  if (a.started) a.has_state = a.started[b];
   const int per_b = a.T * a.s * (a.OC >> 2);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per_b; i += gridDim.x * blockDim.x) {
     const int c4 = i % (a.OC >> 2), o = i / (a.OC >> 2);
@@ -2282,6 +2290,60 @@ __global__ void convtr_overlap_add_kernel(OverlapAddArgs a) {
     if (a.Y) *reinterpret_cast<float4*>(a.Y + a.ymap.off(m) + co) = v;
     if (a.Y2) *reinterpret_cast<float4*>(a.Y2 + a.y2map.off(m) + co) = make_float4(dsm_elu(v.x), dsm_elu(v.y), dsm_elu(v.z), dsm_elu(v.w));
   }
+}
+
+// The frame a TTS step completes, assembled where the samples are: State::last_audio_tokens (core/tts_streaming.rs:275-287)
+// with the test of srv/tts.rs:537.  s = the slot's step index before the step.  Row s - acoustic_delay of the slot's token table is
+// complete after this step: codebook 0 was sampled acoustic_delay steps ago (kept in a ring of acoustic_delay + 1 entries per
+// slot), codebooks >= 1 are this step's samples — except row 0, whose codebooks >= 1 the table took at step 0 (the write-back
+// clamps `step - delay` to 0 and keeps the first write), kept in row0.  A slot emits iff it is active, s >= text_audio_delay +
+// acoustic_delay and no token of the row is a pad (>= pad).  Writes the decoder's codes [B][S] and mask [B] of buffer *sel
+// (the host rotates the buffers: a decode of an earlier step may still be reading another one).  One thread per slot.
+struct TtsFrameArgs {
+  const uint32_t* lat;   // [nslots][S] this step's samples (defined for running slots)
+  const uint8_t* mask;   // [nslots] the slot steps
+  const uint8_t* run;    // [nslots] ... and its depformer ran
+  const int32_t* step;   // [nslots]
+  const uint8_t* sel;    // one byte: the buffer this step fills
+  uint32_t* ring;        // [nslots][ad + 1]
+  uint32_t* row0;        // [nslots][S]
+  uint32_t* codes;       // buffer 0 of this group's slots; buffer i at + i * codes_stride
+  uint8_t* valid;        // likewise, + i * valid_stride
+  long codes_stride, valid_stride;
+  int nslots, S, ad, tad;
+  uint32_t pad;
+};
+__global__ void tts_frame_kernel(TtsFrameArgs a) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.nslots) return;
+  const int sel = *a.sel, S = a.S, ad = a.ad;
+  uint32_t* codes = a.codes + (long)sel * a.codes_stride + (long)b * S;
+  const uint32_t* lat = a.lat + (long)b * S;
+  const bool run = a.run[b] != 0;
+  bool ok = false;
+  if (a.mask[b]) {
+    const int s = a.step[b];
+    uint32_t* ring = a.ring + (long)b * (ad + 1);
+    const uint32_t c0 = run ? lat[0] : a.pad;
+    ring[s % (ad + 1)] = c0;
+    if (s == 0)
+      for (int k = 1; k < S; ++k) a.row0[(long)b * S + k] = run ? lat[k] : a.pad;
+    if (s >= a.tad + ad) {
+      ok = true;
+      const bool first_row = ad > 0 && s == ad;
+      for (int k = 0; k < S; ++k) {
+        uint32_t tok;
+        if (k == 0) tok = ad > 0 ? ring[(s - ad) % (ad + 1)] : c0;
+        else if (first_row) tok = a.row0[(long)b * S + k];
+        else tok = run ? lat[k] : a.pad;
+        ok = ok && tok < a.pad;
+        codes[k] = tok < a.pad ? tok : 0u;
+      }
+    }
+  }
+  if (!ok)
+    for (int k = 0; k < S; ++k) codes[k] = 0u;
+  a.valid[(long)sel * a.valid_stride + b] = ok ? 1 : 0;
 }
 
 __global__ void fill_u32_kernel(uint32_t* p, uint32_t v, long n) {

@@ -3,7 +3,9 @@
 // non-batched transformer the TTS worker builds: srv/tts.rs:345), text-token rule, then the DepFormer — num_slices
 // sequential passes of one shared transformer whose KV sequence is the slice axis (core/lm.rs:640-684).  The per-slot
 // delayed-streams bookkeeping (core/tts_streaming.rs:117-242) is integer work on the host, one upload and one
-// download per step.
+// download per step.  With a Mimi attached (dsm_tts_attach_mimi) dsm_tts_step_pcm also decodes the frame each step completes,
+// on the engine's second stream (the audio_processing_loop of srv/tts.rs:528-544): the frame is assembled on the device
+// (tts_frame_kernel) and the decode of step n overlaps the LM of step n + 1.
 
 namespace {
 
@@ -58,7 +60,7 @@ struct dsm_tts {
   std::vector<Grp> groups;
   // pinned staging
   int32_t *h_tokens = nullptr, *h_allowed = nullptr;
-  uint8_t* h_flags = nullptr;  // [4][B]: mask, force_eop, run, forced
+  uint8_t* h_flags = nullptr;  // [4][B]: mask, force_eop, run, forced; [3][R] row flags; then (4-byte aligned) step_idx [B] i32, frame buffer u8
   uint32_t *h_text_token = nullptr, *h_lat = nullptr;
   // tts_streaming::State per slot
   struct Item {
@@ -67,6 +69,26 @@ struct dsm_tts {
   };
   std::vector<Item> items;
   size_t n_steps = 0;
+  // ---- generated frames -> PCM (dsm_tts_attach_mimi / dsm_tts_step_pcm) ----
+  // tts_frame_kernel ends every group's step body: it keeps the last acoustic_delay + 1 codebook-0 samples of every slot and
+  // writes the decoder's codes / mask of frame buffer *d_fsel.  Buffers 0 and 1 alternate between consecutive step_pcm calls (the
+  // decode of the previous step may still read the other one); buffer 2 takes the frames of token-only dsm_tts_step calls.
+  size_t flags_bytes = 0, step_off = 0;  // the per-step upload: size, offset of the step indices (the buffer byte follows them)
+  int32_t* d_step = nullptr;
+  uint8_t* d_fsel = nullptr;
+  uint32_t *d_ring = nullptr, *d_row0 = nullptr, *d_fcodes = nullptr;  // [B][ad + 1], [B][S], [3][B][S]
+  uint8_t* d_fvalid = nullptr;                                          // [3][B]
+  bool mimi = false;
+  hipEvent_t ev_frames = nullptr;
+  struct PcmEntry {  // one deferred step: its PCM / valid land in pinned memory behind `ev`
+    hipEvent_t ev = nullptr;
+    float* h_pcm = nullptr;     // [B][DSM_FRAME_SIZE]
+    uint8_t* h_valid = nullptr; // [B]
+    bool launched = false;      // false: no slot could emit, nothing was enqueued, valid is all zero
+  };
+  PcmEntry pcm_q[2];
+  uint64_t pcm_seq = 0;  // step_pcm calls so far: entry / frame buffer of call n is n & 1
+  int pcm_pending = 0;   // entries queued and not yet delivered (the oldest is (pcm_seq - pcm_pending) & 1)
 };
 
 namespace {
@@ -94,6 +116,7 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
     int hd = tc->d_model / tc->num_heads;
     if (hd != 32 && hd != 64 && hd != 128) { e->set_error("head_dim %d unsupported (32, 64, 128)", hd); return DSM_ERR_INVALID; }
   }
+  if (c.acoustic_delay < 0 || c.text_audio_delay_in_tokens < 0) { e->set_error("negative delay"); return DSM_ERR_INVALID; }
   if (c.dep_low_rank % 4) { e->set_error("low_rank_embeddings must be a multiple of 4"); return DSM_ERR_INVALID; }
   if (c.cross_attention && (c.ca_max_len <= 0 || c.ca_dim < 0 || (c.ca_dim % 4) != 0)) {
     e->set_error("cross_attention needs ca_max_len > 0 and a ca_dim that is a multiple of 4 (0 = d_model)");
@@ -272,7 +295,15 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
   if ((rc = e->dalloc(&t->d_tokens, (size_t)R * (1 + c.audio_codebooks)))) return rc;
   if ((rc = e->dalloc(&t->d_allowed, B))) return rc;
   // one upload per step: [mask | force_eop | run | forced] per slot, then [row mask | row run | row attends its source] per row
-  if ((rc = e->dalloc(&t->d_mask, (size_t)4 * B + (size_t)3 * R))) return rc;
+  t->step_off = ((size_t)4 * B + (size_t)3 * R + 3) & ~(size_t)3;
+  t->flags_bytes = t->step_off + sizeof(int32_t) * (size_t)B + 4;
+  if ((rc = e->dalloc(&t->d_mask, t->flags_bytes))) return rc;
+  t->d_step = reinterpret_cast<int32_t*>(t->d_mask + t->step_off);
+  t->d_fsel = t->d_mask + t->step_off + sizeof(int32_t) * (size_t)B;
+  if ((rc = e->dalloc(&t->d_ring, (size_t)B * (c.acoustic_delay + 1)))) return rc;
+  if ((rc = e->dalloc(&t->d_row0, (size_t)B * S))) return rc;
+  if ((rc = e->dalloc(&t->d_fcodes, (size_t)3 * B * S))) return rc;
+  if ((rc = e->dalloc(&t->d_fvalid, (size_t)3 * B))) return rc;
   t->d_force_eop = t->d_mask + B;
   t->d_run = t->d_mask + 2 * B;
   t->d_forced = t->d_mask + 3 * B;
@@ -369,7 +400,8 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
   }
   HIPCHK(hipHostMalloc((void**)&t->h_tokens, sizeof(int32_t) * (size_t)R * (1 + c.audio_codebooks)));
   HIPCHK(hipHostMalloc((void**)&t->h_allowed, sizeof(int32_t) * (size_t)B));
-  HIPCHK(hipHostMalloc((void**)&t->h_flags, (size_t)4 * B + (size_t)3 * R));
+  HIPCHK(hipHostMalloc((void**)&t->h_flags, t->flags_bytes));
+  memset(t->h_flags, 0, t->flags_bytes);
   HIPCHK(hipHostMalloc((void**)&t->h_text_token, sizeof(uint32_t) * (size_t)B));
   HIPCHK(hipHostMalloc((void**)&t->h_lat, sizeof(uint32_t) * (size_t)B * S));
   t->n_steps = (size_t)c.max_steps + c.acoustic_delay;
@@ -526,6 +558,52 @@ int tts_group_body(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp, bool run_dep) 
   e->tag_attn[sid] = DSM_PROF_OTHER;
   if (run_dep)
     if ((rc = tts_depformer(t, st, grp))) return rc;
+  {  // the frame this step completes, for the decoder (behind the last sampler launch)
+    const int S = c.dep_num_slices;
+    TtsFrameArgs fa;
+    fa.lat = t->d_lat + (size_t)b0 * S; fa.mask = t->d_mask + b0; fa.run = t->d_run + b0; fa.step = t->d_step + b0;
+    fa.sel = t->d_fsel;
+    fa.ring = t->d_ring + (size_t)b0 * (c.acoustic_delay + 1); fa.row0 = t->d_row0 + (size_t)b0 * S;
+    fa.codes = t->d_fcodes + (size_t)b0 * S; fa.valid = t->d_fvalid + b0;
+    fa.codes_stride = (long)t->B * S; fa.valid_stride = t->B;
+    fa.nslots = nslots; fa.S = S; fa.ad = c.acoustic_delay; fa.tad = c.text_audio_delay_in_tokens;
+    fa.pad = (uint32_t)c.audio_vocab_size - 1;
+    hipLaunchKernelGGL(tts_frame_kernel, dim3((nslots + 63) / 64), dim3(64), 0, st, fa);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+
+// Mimi::decode_step of the frames buffer `sel` holds, on the decode stream behind the step's groups; PCM and valid flags go
+// to the entry's pinned buffers, its event closes the sequence.
+int tts_enqueue_decode(dsm_tts* t, int sel, dsm_tts::PcmEntry& en) {
+  dsm_engine* e = t->eng;
+  const int B = t->B, S = t->cfg.dep_num_slices;
+  hipStream_t sd = e->s_enc;
+  MimiDecState& d = e->dec;
+  HIPCHK(hipEventRecord(t->ev_frames, e->s_model));  // the model stream has joined every group
+  HIPCHK(hipStreamWaitEvent(sd, t->ev_frames, 0));
+  HIPCHK(hipMemcpyAsync(d.codes, t->d_fcodes + (size_t)sel * B * S, sizeof(uint32_t) * (size_t)B * S, hipMemcpyDeviceToDevice, sd));
+  HIPCHK(hipMemcpyAsync(d.mask, t->d_fvalid + (size_t)sel * B, (size_t)B, hipMemcpyDeviceToDevice, sd));
+  if (int rc = mimi_decode(e, sd)) return rc;
+  HIPCHK(hipMemcpyAsync(en.h_pcm, d.pcm, sizeof(float) * (size_t)B * DSM_FRAME_SIZE, hipMemcpyDeviceToHost, sd));
+  HIPCHK(hipMemcpyAsync(en.h_valid, d.mask, (size_t)B, hipMemcpyDeviceToHost, sd));
+  HIPCHK(hipEventRecord(en.ev, sd));
+  en.launched = true;
+  return 0;
+}
+
+// the oldest pending entry: wait for it, hand it out
+int tts_deliver_pcm(dsm_tts* t, float* pcm_out, uint8_t* pcm_valid_out) {
+  dsm_engine* e = t->eng;
+  dsm_tts::PcmEntry& en = t->pcm_q[(t->pcm_seq - (uint64_t)t->pcm_pending) & 1];
+  if (en.launched) HIPCHK(hipEventSynchronize(en.ev));
+  for (int b = 0; b < t->B; ++b) {
+    const bool v = en.launched && en.h_valid[b];
+    if (pcm_valid_out) pcm_valid_out[b] = v ? 1 : 0;
+    if (pcm_out && v) memcpy(pcm_out + (size_t)b * DSM_FRAME_SIZE, en.h_pcm + (size_t)b * DSM_FRAME_SIZE, sizeof(float) * DSM_FRAME_SIZE);
+  }
+  t->pcm_pending -= 1;
   return 0;
 }
 
@@ -543,8 +621,11 @@ void dsm_tts_destroy(dsm_tts* t) {
     (void)hipSetDevice(t->eng->device);
     (void)hipDeviceSynchronize();
   }
-  for (void* p : {(void*)t->h_tokens, (void*)t->h_allowed, (void*)t->h_flags, (void*)t->h_text_token, (void*)t->h_lat})
+  for (void* p : {(void*)t->h_tokens, (void*)t->h_allowed, (void*)t->h_flags, (void*)t->h_text_token, (void*)t->h_lat,
+                  (void*)t->pcm_q[0].h_pcm, (void*)t->pcm_q[1].h_pcm, (void*)t->pcm_q[0].h_valid, (void*)t->pcm_q[1].h_valid})
     if (p) (void)hipHostFree(p);
+  for (hipEvent_t ev : {t->ev_frames, t->pcm_q[0].ev, t->pcm_q[1].ev})
+    if (ev) (void)hipEventDestroy(ev);
   dsm_destroy(t->eng);
   delete t;
 }
@@ -567,9 +648,13 @@ int dsm_tts_create(const dsm_tts_config* cfg, int device_id, int batch_size, con
   return 0;
 }
 
-int dsm_tts_step(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* allowed, const uint8_t* mask,
-                 uint32_t* text_token_out, uint32_t* audio_out) {
-  if (!t || !prev_text_token || !allowed || !mask) return DSM_ERR_INVALID;
+}  // extern "C" (reopened below)
+
+namespace {
+// State::step.  decode: also queue the decode of the frame the step completes as the next entry of the PCM queue (the caller
+// checked that the entry is free); otherwise the frame goes to the spare buffer and is dropped.
+int tts_step_impl(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* allowed, const uint8_t* mask,
+                  uint32_t* text_token_out, uint32_t* audio_out, bool decode) {
   dsm_engine* e = t->eng;
   const dsm_tts_config& c = t->cfg;
   const int B = t->B, S = c.dep_num_slices, nc = c.audio_codebooks;
@@ -580,6 +665,9 @@ int dsm_tts_step(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* all
   const int rps = t->rps, R = t->R;
   uint8_t *h_mask = t->h_flags, *h_force = t->h_flags + B, *h_run = t->h_flags + 2 * B, *h_forced = t->h_flags + 3 * B;
   uint8_t *h_rmask = t->h_flags + 4 * B, *h_rrun = h_rmask + R, *h_ca_act = h_rrun + R;
+  int32_t* h_step = reinterpret_cast<int32_t*>(t->h_flags + t->step_off);
+  const int fsel = decode ? (int)(t->pcm_seq & 1) : 2;
+  t->h_flags[t->step_off + sizeof(int32_t) * (size_t)B] = (uint8_t)fsel;
   // A slot whose previous step returned "max step-idx reached" has step_idx == n_steps: the reference's next
   // `self.text_tokens[self.step_idx]` (core/tts_streaming.rs:199) is an out-of-bounds panic.  Here: refuse the whole
   // step before anything is touched, the caller resets the slot (or masks it out).
@@ -599,6 +687,7 @@ int dsm_tts_step(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* all
     h_force[b] = it.consecutive_pads > (size_t)c.max_consecutive_pads;
     h_run[b] = mask[b] && step >= (size_t)c.text_audio_delay_in_tokens;  // :203-205
     h_forced[b] = step < (size_t)c.acoustic_delay;
+    h_step[b] = (int32_t)step;
     for (int j = 0; j < rps; ++j) {  // batch_size = if cfg_alpha.is_some() { 2 } else { 1 } — :122: the second row only runs when the slot is guided
       const int r = b * rps + j;
       h_rmask[r] = h_mask[b] && (j == 0 || t->cfg_on[b]);
@@ -624,7 +713,7 @@ int dsm_tts_step(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* all
   }
   HIPCHK(hipMemcpyAsync(t->d_tokens, t->h_tokens, sizeof(int32_t) * (size_t)R * (1 + nc), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(t->d_allowed, t->h_allowed, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(t->d_mask, t->h_flags, (size_t)4 * B + (size_t)3 * R, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t->d_mask, t->h_flags, t->flags_bytes, hipMemcpyHostToDevice, st));
   // The whole device side of a group's step — ~45 launches for the main LM, ~44 per depformer slice — is one hipGraph per
   // group once its two variants (with / without the depformer) have each run twice: the step is launch-bound otherwise.
   // Groups fork from the model stream behind the uploads and join it again before the downloads.
@@ -645,6 +734,17 @@ int dsm_tts_step(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* all
     if (g > 0) HIPCHK(hipEventRecord(e->ev_grp_done[g], gs));
   }
   for (size_t g = 1; g < Gn; ++g) HIPCHK(hipStreamWaitEvent(st, e->ev_grp_done[g], 0));  // join: only after every group was launched
+  if (decode) {  // the entry is queued whatever happens: a slot can emit from step text_audio_delay + acoustic_delay on
+    dsm_tts::PcmEntry& en = t->pcm_q[fsel];
+    en.launched = false;
+    t->pcm_seq += 1;
+    t->pcm_pending += 1;
+    bool any = false;
+    for (int b = 0; b < B; ++b)
+      any = any || (mask[b] && t->items[b].step_idx >= (size_t)(c.text_audio_delay_in_tokens + c.acoustic_delay));
+    if (any)
+      if (int rc = tts_enqueue_decode(t, fsel, en)) return rc;
+  }
   HIPCHK(hipMemcpyAsync(t->h_text_token, t->d_text_token, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
   bool any_run = false;
   for (int b = 0; b < B; ++b) any_run = any_run || h_run[b];
@@ -671,6 +771,86 @@ int dsm_tts_step(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* all
   }
   return ret;
 }
+}  // namespace
+
+extern "C" {
+
+int dsm_tts_step(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* allowed, const uint8_t* mask,
+                 uint32_t* text_token_out, uint32_t* audio_out) {
+  if (!t || !prev_text_token || !allowed || !mask) return DSM_ERR_INVALID;
+  return tts_step_impl(t, prev_text_token, allowed, mask, text_token_out, audio_out, false);
+}
+
+int dsm_tts_attach_mimi(dsm_tts* t, const dsm_mimi_config* mimi, const char* mimi_safetensors) {
+  if (!t || !mimi || !mimi_safetensors) {
+    if (!t) g_create_error = "null argument";
+    return DSM_ERR_INVALID;
+  }
+  dsm_engine* e = t->eng;
+  const dsm_tts_config& c = t->cfg;
+  if (t->mimi) { e->set_error("a Mimi is attached already"); return DSM_ERR_STATE; }
+  // srv/tts.rs:309-310: mimi::load(.., Some(audio_codebooks)); every generated token must be a codebook entry
+  if (mimi->quantizer_n_q != c.dep_num_slices || mimi->quantizer_bins < c.audio_vocab_size - 1) {
+    e->set_error("Mimi with n_q %d / %d bins does not decode frames of %d codebooks with tokens below %d", mimi->quantizer_n_q,
+                 mimi->quantizer_bins, c.dep_num_slices, c.audio_vocab_size - 1);
+    return DSM_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  std::unique_lock<std::shared_mutex> alone(e->api_mu);  // allocations (null-stream fills) must not run beside a capture
+  HIPCHK(hipDeviceSynchronize());
+  char err[512];
+  dsm_st_file* f = dsm_st_open(mimi_safetensors, err, sizeof err);
+  if (!f) { e->set_error("%s", err); return DSM_ERR_IO; }
+  Loader ld{e, f};
+  int rc = load_mimi(e, ld, &e->mimi_w, *mimi);
+  dsm_st_close(f);
+  if (rc) return rc;
+  if (!e->mimi_w.has_decoder) { e->set_error("the Mimi checkpoint has no decoder.* tensors"); return DSM_ERR_STATE; }
+  const int B = t->B;
+  if ((rc = alloc_dec_state(e))) return rc;
+  if (e->dec.h_descs.empty()) { e->set_error("a decoder without streaming convolutions is not supported"); return DSM_ERR_INVALID; }
+  if ((rc = e->dalloc(&e->dec.started, B))) return rc;
+  HIPCHK(hipEventCreateWithFlags(&t->ev_frames, hipEventDisableTiming));
+  for (dsm_tts::PcmEntry& en : t->pcm_q) {
+    HIPCHK(hipEventCreateWithFlags(&en.ev, hipEventDisableTiming));
+    HIPCHK(hipHostMalloc((void**)&en.h_pcm, sizeof(float) * (size_t)B * DSM_FRAME_SIZE));
+    HIPCHK(hipHostMalloc((void**)&en.h_valid, (size_t)B));
+  }
+  HIPCHK(hipDeviceSynchronize());
+  t->mimi = true;
+  return 0;
+}
+
+int dsm_tts_step_pcm(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* allowed, const uint8_t* mask,
+                     uint32_t* text_token_out, uint32_t* audio_out, float* pcm_out, uint8_t* pcm_valid_out) {
+  if (!t || !prev_text_token || !allowed || !mask) return DSM_ERR_INVALID;
+  dsm_engine* e = t->eng;
+  if (!t->mimi) { e->set_error("dsm_tts_step_pcm needs dsm_tts_attach_mimi first"); return DSM_ERR_STATE; }
+  if (pcm_out && t->pcm_pending > 0) {
+    e->set_error("%d deferred step(s) wait for dsm_tts_recv_pcm: a serial step would deliver out of order", t->pcm_pending);
+    return DSM_ERR_STATE;
+  }
+  if (t->pcm_pending >= 2) { e->set_error("two deferred steps wait for dsm_tts_recv_pcm"); return DSM_ERR_STATE; }
+  const uint64_t seq = t->pcm_seq;
+  const int rc = tts_step_impl(t, prev_text_token, allowed, mask, text_token_out, audio_out, true);
+  if (pcm_out && t->pcm_seq != seq) {  // serial: the entry this call queued is delivered at once
+    ApiShared api(e);
+    if (int rd = tts_deliver_pcm(t, pcm_out, pcm_valid_out)) return rd;
+  }
+  return rc;
+}
+
+int dsm_tts_recv_pcm(dsm_tts* t, float* pcm_out, uint8_t* pcm_valid_out) {
+  if (!t) return DSM_ERR_INVALID;
+  if (t->pcm_pending == 0) return 0;
+  dsm_engine* e = t->eng;
+  HIPCHK(hipSetDevice(e->device));
+  ApiShared api(e);
+  if (int rc = tts_deliver_pcm(t, pcm_out, pcm_valid_out)) return rc;
+  return 1;
+}
+
+int dsm_tts_pcm_pending(dsm_tts* t) { return t ? t->pcm_pending : DSM_ERR_INVALID; }
 
 int dsm_tts_get_metrics(dsm_tts* t, dsm_metrics* out) {
   if (!t || !out) return DSM_ERR_INVALID;
@@ -831,6 +1011,24 @@ int dsm_tts_reset_slot(dsm_tts* t, int slot) {
   for (int j = 0; j < t->rps; ++j)
     if (int rc = reset_transformer_slot(e, e->s_model, t->tr, slot * t->rps + j)) return rc;
   HIPCHK(hipStreamSynchronize(e->s_model));
+  if (t->mimi) {
+    // The slot's next generation decodes with a fresh Mimi (srv/tts.rs:499-500: clone() + reset_state()): conv states and carries
+    // zero, not started, and — unlike Mimi::reset_batch_idx — the decoder transformer back at position 0.  On the decode stream,
+    // i.e. behind the decodes already queued for the old generation.
+    hipStream_t sd = e->s_enc;
+    MimiDecState& d = e->dec;
+    const MimiW& w = e->mimi_w;
+    hipLaunchKernelGGL(conv_state_reset_kernel, dim3((unsigned)d.h_descs.size()), dim3(256), 0, sd, d.descs, slot);
+    HIPCHK(hipGetLastError());
+    for (size_t i = 0; i < w.dec_stages.size(); ++i) {
+      const size_t n = (size_t)(w.dec_stages[i].k - w.dec_stages[i].stride) * w.dec_stages[i].out_c;
+      HIPCHK(hipMemsetAsync(d.stages[i].carry + (size_t)slot * n, 0, n * sizeof(float), sd));
+    }
+    const size_t n = (size_t)w.cfg.downsample_stride * w.cfg.dimension;
+    HIPCHK(hipMemsetAsync(d.up_carry + (size_t)slot * n, 0, n * sizeof(float), sd));
+    HIPCHK(hipMemsetAsync(d.started + slot, 0, 1, sd));
+    if (int rc = reset_transformer_slot(e, sd, d.tr, slot)) return rc;
+  }
   return 0;
 }
 

@@ -360,6 +360,35 @@ int dsm_tts_set_sampling(dsm_tts*, int slot, int top_k, float temperature, uint6
  *     core/lm.rs:718-721: Tensor * f64 = affine(mul as f32, 0)), sampling once per slot.
  * Needs cfg.cross_attention; n, n_uncond <= ca_max_len.  dsm_tts_reset_slot clears both (a fresh State). */
 int dsm_tts_set_ca_src(dsm_tts*, int slot, const float* ca_src, int n, const float* ca_src_uncond, int n_uncond, double cfg_alpha);
+/* Generated frames to PCM — what the reference's TTS worker does with every step's tokens: a second thread receives
+ * state.last_audio_tokens() and runs Mimi::decode_step on them (srv/tts.rs:528-544, core/mimi.rs:217-225) while the inference
+ * loop is already in its next step.
+ *   dsm_tts_attach_mimi   the Mimi for the generated frames (srv/tts.rs:309-310 mimi::load(audio_tokenizer_file,
+ *     Some(audio_codebooks))), loaded into this object: no LM checkpoint of an STT engine is involved.  DSM_ERR_INVALID unless
+ *     quantizer_n_q == dep_num_slices and quantizer_bins >= audio_vocab_size - 1; DSM_ERR_STATE when the checkpoint has no
+ *     decoder.* tensors or a Mimi is attached already.
+ *   dsm_tts_step_pcm      State::step (tokens, audio_out, step indices and the dsm_tts_audio_tokens table exactly as dsm_tts_step)
+ *     + the audio_processing_loop's decode of the frame this step completed.  With s the slot's step index before the call, a
+ *     slot emits iff mask[b], s >= text_audio_delay_in_tokens + acoustic_delay and no token of audio_tokens[s - acoustic_delay]
+ *     is >= audio_vocab_size - 1 (last_audio_tokens, core/tts_streaming.rs:275-287, and the test at srv/tts.rs:537): codebook 0
+ *     of that row was sampled acoustic_delay steps ago, codebooks >= 1 by this step.  pcm_valid_out[b] is that predicate; the
+ *     1920 samples of a slot that did not emit are left alone.  The frame is assembled on the device and decoded on the engine's
+ *     second stream.  pcm_out != NULL: the call waits for the decode (serial).  pcm_out == NULL: the decode is only enqueued
+ *     and the step's entry (PCM + valid, also when no slot emits) waits in a queue of two, so that the decode of step n overlaps
+ *     the LM of step n + 1.  DSM_ERR_STATE, nothing touched: no Mimi attached; a third deferred step while two entries wait;
+ *     a serial call while any waits.
+ *   dsm_tts_recv_pcm      the oldest waiting entry: 1 = delivered (pcm_out [B*1920] and pcm_valid_out [B] may be NULL), 0 = none.
+ *   dsm_tts_pcm_pending   entries waiting (0..2).
+ * Every slot decodes as a Mimi of its own, fresh at the slot's first frame and again after dsm_tts_reset_slot — the reference
+ * decodes every request with clone() + reset_state() (srv/tts.rs:499-500), never with one batched module: a slot that starts after
+ * the batch's first frame gets no carry term in its first frame, and dsm_tts_reset_slot also puts the decoder transformer back
+ * to position 0 (dsm_mimi_reset_slot, like Mimi::reset_batch_idx, does not).  Frames queued before a reset are still delivered. */
+int dsm_tts_attach_mimi(dsm_tts*, const dsm_mimi_config* mimi, const char* mimi_safetensors);
+int dsm_tts_step_pcm(dsm_tts*, const uint32_t* prev_text_token, const int32_t* allowed, const uint8_t* mask,
+                     uint32_t* text_token_out, uint32_t* audio_out,
+                     float* pcm_out /* [B*1920] or NULL = deferred */, uint8_t* pcm_valid_out /* [B] */);
+int dsm_tts_recv_pcm(dsm_tts*, float* pcm_out, uint8_t* pcm_valid_out);
+int dsm_tts_pcm_pending(dsm_tts*);
 int dsm_tts_debug_read(dsm_tts*, const char* name, float* out, size_t cap); /* "lm.hidden", "lm.logits": one row per BATCH ROW (2 per slot with cfg_rows) */
 int dsm_tts_get_metrics(dsm_tts*, dsm_metrics* out); /* graph_launches / eager_bodies only */
 
