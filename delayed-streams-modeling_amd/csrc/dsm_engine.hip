@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/dsm.h"
+#include "dsm_device.h"
 #include "dsm_config_presets.h"
 #include "dsm_kernels.h"
 #include "dsm_numerics.h"
@@ -29,15 +30,34 @@
 
 static thread_local std::string g_create_error;
 
-#define HIPCHK_E(eng, expr)                                                                         \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) {                                                                         \
-      (eng)->set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);  \
-      return DSM_ERR_DEVICE;                                                                        \
-    }                                                                                               \
-  } while (0)
-#define HIPCHK(expr) HIPCHK_E(e, expr)
+// The library's whole environment: ten DSM_* variables (include/dsm.h lists them), read once per engine by DsmDevice::open
+// after dot_mode is set.  dsm_env_int is the only getenv in csrc/; the two group counts (DSM_LM_GROUPS, DSM_TTS_GROUPS) go
+// through it where they are computed.
+static int dsm_env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+static void dsm_read_env(DsmDevice* e, bool stt) {
+  // dot_mode 1, STT engine only: the bx3 loop is cheaper per tile, so whole-K workgroups pay from 192 (n, m) tiles on (r03 sweep,
+  // profiles/r03/experiments/chunk_loop_min_mode1.txt: B = 400 13.2 -> 12.0 ms, B = 1024 27.9 -> 26.7), and the bf16 GEMMs leave
+  // the vector ALU to the attention waves, so large attention launches run three workgroups per CU (r03: 52.1 -> 50.4 ms at
+  // B = 2048, 59.8 -> 56.9 at 2304; four: 53.7).  The TTS engine has always kept 384 and 60000 in both modes (it never ran
+  // these two lines); the difference is kept on purpose: dropping it would change which kernels a TTS step launches.
+  if (stt && e->dot_mode == 1) {
+    e->chunk_loop_min_tiles = 192;
+    e->attn_lds_pad = 40000;
+  }
+  e->use_graphs = dsm_env_int("DSM_GRAPHS", 1) != 0;
+  e->fuse_qkv = dsm_env_int("DSM_FUSE_QKV", 1) != 0;
+  e->stream_prio = dsm_env_int("DSM_STREAM_PRIO", 0) != 0;  // the TTS engine's two streams have no priorities: ignored there
+  e->fuse_front = dsm_env_int("DSM_FUSE_FRONT", 0) != 0;
+  e->chunk_loop_min_tiles = dsm_env_int("DSM_CHUNK_LOOP_MIN", e->chunk_loop_min_tiles);
+  e->loop_depth = dsm_env_int("DSM_LOOP_DEPTH", 4) == 2 ? 2 : 4;
+  e->smallk_min_tiles = dsm_env_int("DSM_SMALLK_MIN", e->smallk_min_tiles);
+  const int mt = dsm_env_int("DSM_SMALLK_MT", e->smallk_mt);
+  if (mt == 1 || mt == 2 || mt == 4) e->smallk_mt = mt;
+}
+
 
 namespace {
 
@@ -149,6 +169,8 @@ struct MimiState {  // one per side (encoder-thread clone / model side)
 
 struct MimiDecState {  // Mimi::decode_step state, allocated on first use
   bool ready = false, first_call = true;
+  DsmDevice::GraphSlot* graph = nullptr;  // one decode_step
+  float* h_pcm_out = nullptr;             // pinned [B][DSM_FRAME_SIZE]: the host-pointer entry point's download
   uint32_t* codes = nullptr;
   uint8_t* mask = nullptr;
   // [B], TTS decode path only (dsm_tts_attach_mimi): a slot behaves as a fresh module of its own — the carry terms follow this
@@ -176,9 +198,15 @@ struct LmW {
   Linear text_linear, extra_heads;
 };
 
+// The activation scratch of one LM transformer_forward: x (in / out), xn, q, att [rows][d] and g [rows][hidden]
+struct ActScratch {
+  float *x = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *g = nullptr;
+  ActScratch from_row(size_t r0, int d, int hid) const { return {x + r0 * d, xn + r0 * d, q + r0 * d, att + r0 * d, g + r0 * hid}; }
+};
+
 struct LmState {
-  float *x = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *g = nullptr, *hidden = nullptr, *logits = nullptr,
-        *eh = nullptr, *prs = nullptr;
+  ActScratch act;
+  float *hidden = nullptr, *logits = nullptr, *eh = nullptr, *prs = nullptr;
   uint32_t *next_cb = nullptr, *text_token = nullptr, *text_out = nullptr, *codes_in = nullptr;
   uint8_t *first_step = nullptr, *mask = nullptr;
   uint32_t* rng_key = nullptr;             // [B][8] ChaCha12 key per slot (temperature > 0: lm_gumbel_kernel; dsm_asr_set_seed)
@@ -203,30 +231,14 @@ struct HostItem {  // ItemState — core/asr.rs:15-51 (word assembly stays on th
 
 }  // namespace
 
-struct dsm_engine {
+// The STT product on its device context: configuration, Mimi (weights, the two encoder states, the decode state), the LM,
+// pinned staging, word assembly, metrics and the encoder -> model pipeline.  Device memory, pinned memory, events and graph
+// slots come from DsmDevice and are released by its destructor.
+struct dsm_engine : DsmDevice {
   dsm_asr_config cfg{};
-  int B = 0, device = 0;
-  hipStream_t s_enc = nullptr, s_model = nullptr;
-  static constexpr int kMaxGroups = 4;
-  hipStream_t s_grp[kMaxGroups] = {nullptr, nullptr, nullptr, nullptr};  // s_grp[0] is unused (group 0 runs on s_model)
-  hipEvent_t ev_fork = nullptr, ev_grp_in[kMaxGroups] = {}, ev_grp_done[kMaxGroups] = {}, ev_stagger[kMaxGroups] = {};
+  int B = 0;
+  hipEvent_t ev_grp_in[kMaxGroups] = {}, ev_stagger[kMaxGroups] = {};
   bool grp_busy = false;
-  // ---- the ten DSM_* environment variables (read by dsm_read_env below, listed in include/dsm.h) and what they start from ----
-  bool use_graphs = true;       // DSM_GRAPHS=0: every launch sequence stays eager (GraphSlot below)
-  bool fuse_qkv = true;         // DSM_FUSE_QKV=0: keep the separate QKV reduce launch
-  bool stream_prio = false;     // DSM_STREAM_PRIO=1: LM streams high, encoder stream low (STT engine)
-  // DSM_FUSE_FRONT=1: the SEANet front end as one fused kernel (seanet_front_kernel) instead of three GEMM launches.  Off by
-  // default: with the fused kernel in the encoder stream, an encode that overlaps the LM's dot_mode 1 kernels on the same CUs
-  // emits codes that differ from run to run; the three launches are bit-reproducible and cost ~2 % per step
-  bool fuse_front = false;
-  int chunk_loop_min_tiles = 384;  // DSM_CHUNK_LOOP_MIN: whole-K workgroups from this many (n, m) tiles on (swept at B = 512 / 1024: 384 best)
-  int loop_depth = 4;           // DSM_LOOP_DEPTH=2: two-block rolling window (fewer registers, three waves per SIMD) where four is the default
-  int smallk_min_tiles = 1024;  // DSM_SMALLK_MIN: one-chunk GEMMs (K <= 256) move to gemm_loop_kernel from this many 64-row tiles on
-  int smallk_mt = 4;            // DSM_SMALLK_MT: 16-row tiles per workgroup of those launches
-  // ---- fixed per engine and dot_mode (dsm_read_env) ----
-  size_t attn_lds_pad = 60000;  // extra dynamic LDS per attention workgroup of a large launch (2 per CU; 40000 = 3 per CU)
-  int dot_mode = 0;             // dsm_asr_config.dot_mode / dsm_tts_config.dot_mode: 1 = the bf16-weight GEMMs in "bx3" (gemm_bx3_kernel)
-  int prio_hi = 0;
   bool serialize_groups = false;  // dsm_debug_serialize_groups: every group on the model stream (profiling aid)
   hipEvent_t ev_codes_consumed = nullptr;
   bool codes_consumed_valid = false;
@@ -239,11 +251,9 @@ struct dsm_engine {
   std::atomic<bool> mimi1_ready{false};
   std::mutex mimi1_mu;
   MimiDecState dec;
-  float* h_pcm_out = nullptr;
   LmW lm_w;
   LmState lm;
-  std::vector<void*> allocs;
-  std::string err;
+  GraphSlot *g_enc[2] = {}, *g_grp[kMaxGroups] = {};  // one Mimi encode per side, one LM step per stream group
   // host staging (pinned)
   float* h_pcm = nullptr;
   float* h_pcm1 = nullptr;
@@ -256,39 +266,6 @@ struct dsm_engine {
   std::vector<dsm_asr_msg> msgs;
   std::vector<uint32_t> msg_tokens;
   dsm_metrics metrics{};
-  // split-K workspaces of the tiled GEMM, one per stream (0 = encoder, 1 = model); grown on first use
-  static constexpr int kStreams = 1 + kMaxGroups;
-  float* gemm_ws[kStreams] = {};
-  size_t gemm_ws_cap[kStreams] = {};
-  std::atomic<uint64_t> ws_gen{0};  // bumped whenever a workspace moves: captured graphs hold the old pointer
-  // hipGraph replay of the launch-bound inner loops: the kernel sequence of one Mimi encode / decode,
-  // of one LM stream group's transformer + heads, of one TTS step is captured once its shapes, pointers and first-call
-  // branches have settled (two eager runs), then replayed with ONE hipGraphLaunch — ~150 kernel nodes for ~12 us of
-  // host time instead of ~3.5 us each.  Every per-step variable already lives in device buffers, so the captured
-  // arguments never change.  DSM_GRAPHS=0 keeps the eager path; profiling brackets force it too.
-  struct GraphSlot {
-    hipGraphExec_t exec = nullptr;
-    uint64_t key = 0, ws_gen = 0;
-    int warm = 0;
-    int failures = 0;  // captures of this sequence that did not end in a graph; after kMaxCaptureTries it stays eager
-    bool disabled = false;
-  };
-  static constexpr int kMaxCaptureTries = 3;
-  // capturing: per host thread (the encoder thread may capture while the model thread launches eagerly)
-  static thread_local bool capturing;
-  bool capture_failed = false;
-  GraphSlot g_enc[2], g_grp[kMaxGroups], g_dec, g_ttsg[kMaxGroups][2];
-  std::atomic<uint64_t> graph_launches{0}, eager_bodies{0}, capture_failures{0};
-  std::string capture_error;  // what the first failed capture reported (err_mu)
-  // a capture that did not produce a graph is never silent: counted, its first reason kept for dsm_metrics
-  void note_capture_failure(const char* what, hipError_t he) {
-    capture_failures += 1;
-    std::lock_guard<std::mutex> lk(err_mu);
-    if (capture_error.empty()) {
-      capture_error = what;
-      if (he != hipSuccess) { capture_error += ": "; capture_error += hipGetErrorString(he); }
-    }
-  }
   // run-ahead pipeline between the encoder thread and the model thread (dsm_mimi_encode_step_async /
   // dsm_asr_step_tokens_ticket): the reference's sync_channel(100) of PipelineMsg (srv/batched_asr.rs:291), here a ring of
   // kPipe frames: pinned staging for the PCM + mask, a private device copy of the frame's codes, one event "encoded" and
@@ -305,206 +282,6 @@ struct dsm_engine {
   int pipe_next = 0;
   bool pipe_ready = false;
   std::mutex pipe_mu;
-  // Two host threads may drive one engine (encoder thread || model thread, srv/batched_asr.rs:314,432).  A stream capture
-  // must not see the OTHER thread touch the capturing stream or an event of it: the model thread's dsm_streams_join records
-  // ev_join ON the encoder stream and then makes the model stream wait for it — issued while the encoder thread is between
-  // Begin and EndCapture on that stream, the record lands inside the capture and the wait pulls the model stream into it
-  // (EndCapture then fails as "unjoined" / "invalidated", which is what r02 saw now and then); the same goes for
-  // hipEventSynchronize / hipStreamWaitEvent on ev_done / ev_consumed against a capture on the stream of their last record.
-  // A capture therefore runs alone: every entry point that issues HIP work holds api_mu shared for the whole call,
-  // run_captured trades that for the exclusive side around Begin..Instantiate (a few times per engine lifetime).
-  std::shared_mutex api_mu;
-  static thread_local std::shared_lock<std::shared_mutex>* api_held;
-  // per-kernel-class event timing (dsm_prof_*)
-  unsigned prof_mask = 0;
-  // one slot per stream (0 = encoder, 1 = model): the two host threads of the worker never share a slot
-  int tag_gemm[kStreams] = {DSM_PROF_OTHER, DSM_PROF_OTHER, DSM_PROF_OTHER, DSM_PROF_OTHER, DSM_PROF_OTHER};
-  int tag_attn[kStreams] = {DSM_PROF_OTHER, DSM_PROF_OTHER, DSM_PROF_OTHER, DSM_PROF_OTHER, DSM_PROF_OTHER};
-  std::mutex prof_mu, err_mu;
-  int sid(hipStream_t st) const {  // 0 = encoder, 1 = model (= group 0), 1 + g = group g
-    if (st == s_enc) return 0;
-    for (int g = 1; g < kMaxGroups; ++g)
-      if (st == s_grp[g]) return 1 + g;
-    return 1;
-  }
-  struct ProfRec {
-    int tag;
-    hipEvent_t a, b;
-  };
-  std::vector<ProfRec> prof_recs;
-  std::vector<hipEvent_t> prof_pool;
-  double prof_total_us[DSM_PROF_NTAGS] = {0};
-  uint64_t prof_launches[DSM_PROF_NTAGS] = {0};
-
-  // in-kernel launch brackets (attention kernels): device buffer of (min start, max end) wall-clock pairs
-  static constexpr size_t kDevTsCap = 1 << 16;
-  unsigned long long* dev_ts = nullptr;
-  std::vector<int> dev_ts_tags;  // tag of record i (records are handed out in launch order)
-  std::vector<int> dev_ts_info;  // (stream id << 8) | kind of record i: 0 attention, 1 GEMM, 2 its reduce launch
-  bool timeline = false;         // dsm_prof_timeline: GEMM launches take records too (two each: the GEMM and its reduce)
-  unsigned long long* dev_ts_slot(int tag, int sid_ = 0, int kind = 0, int n = 1) {
-    if (!dev_ts || !(prof_mask & (1u << tag))) return nullptr;
-    std::lock_guard<std::mutex> lk(prof_mu);
-    if (dev_ts_tags.size() + n > kDevTsCap) return nullptr;
-    unsigned long long* p = dev_ts + 2 * dev_ts_tags.size();
-    for (int i = 0; i < n; ++i) {
-      dev_ts_tags.push_back(tag);
-      dev_ts_info.push_back((sid_ << 8) | (kind + i));
-    }
-    return p;
-  }
-
-  hipEvent_t prof_event() {
-    if (!prof_pool.empty()) {
-      hipEvent_t ev = prof_pool.back();
-      prof_pool.pop_back();
-      return ev;
-    }
-    hipEvent_t ev = nullptr;
-    (void)hipEventCreate(&ev);
-    return ev;
-  }
-  // bracket one launch: returns an index to close with prof_end, or -1 when the class is not selected
-  int prof_begin(int tag, hipStream_t st) {
-    if (!(prof_mask & (1u << tag))) return -1;
-    std::lock_guard<std::mutex> lk(prof_mu);
-    ProfRec r{tag, prof_event(), prof_event()};
-    (void)hipEventRecord(r.a, st);
-    prof_recs.push_back(r);
-    return (int)prof_recs.size() - 1;
-  }
-  void prof_end(int h, hipStream_t st) {
-    if (h < 0) return;
-    std::lock_guard<std::mutex> lk(prof_mu);
-    (void)hipEventRecord(prof_recs[h].b, st);
-  }
-
-  void set_error(const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    std::lock_guard<std::mutex> lk(err_mu);
-    err = buf;
-  }
-
-  template <typename T>
-  int dalloc(T** out, size_t count, bool zero = true) {
-    void* p = nullptr;
-    size_t bytes = count * sizeof(T) + 256;  // slack: K-padding reads of the GEMM may run past a row
-    HIPCHK_E(this, hipMalloc(&p, bytes));
-    // hipMemset / hipMemcpy run on the null stream and may return before the device side is done (a pageable H2D copy
-    // returns once the data is staged); the engine's streams are non-blocking, i.e. NOT ordered against the null
-    // stream, so a kernel launched right after (load-time table folds, state fills) could read or be overwritten by
-    // them.  Load time only: wait.
-    if (zero) {
-      HIPCHK_E(this, hipMemset(p, 0, bytes));
-      HIPCHK_E(this, hipStreamSynchronize(nullptr));
-    }
-    allocs.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return 0;
-  }
-  template <typename T>
-  int upload(T** out, const T* host, size_t count) {
-    if (int rc = dalloc(out, count)) return rc;
-    HIPCHK_E(this, hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice));
-    HIPCHK_E(this, hipStreamSynchronize(nullptr));
-    return 0;
-  }
-
-  // ---- weight arena: every immutable weight tensor of the STT engine lives in ONE contiguous device
-  // allocation, carved in load order, so that a multi-GPU launcher can fan the packed weights out with a single RCCL
-  // broadcast and the other ranks attach to the received bytes without reading, converting or packing anything.
-  //   W_PLAIN    no arena: upload_w == upload (the TTS engine)
-  //   W_MEASURE  first pass over the checkpoint: only adds up the carve sizes
-  //   W_LOAD     second pass: carve + host-to-device copy; the answers of the optional-key probes go to `manifest`
-  //   W_ATTACH   carve only: the bytes are already there (received arena); probes replay `manifest`
-  enum WeightMode { W_PLAIN = 0, W_MEASURE, W_LOAD, W_ATTACH };
-  WeightMode wmode = W_PLAIN;
-  char* arena = nullptr;
-  size_t arena_size = 0, arena_off = 0;
-  bool arena_owned = false;
-  std::vector<uint8_t> manifest;
-  size_t manifest_pos = 0;
-  template <typename T>
-  int upload_w(T** out, const T* host, size_t count) {
-    if (wmode == W_PLAIN) return upload(out, host, count);
-    const size_t bytes = (count * sizeof(T) + 256 + 255) & ~(size_t)255;  // same slack as dalloc, 256-byte aligned carves
-    if (wmode != W_MEASURE) {
-      if (arena_off + bytes > arena_size) {
-        set_error("weight arena too small: need %zu bytes at offset %zu of %zu (config / manifest mismatch?)", bytes, arena_off, arena_size);
-        return DSM_ERR_INVALID;
-      }
-      *out = reinterpret_cast<T*>(arena + arena_off);
-      if (wmode == W_LOAD) HIPCHK_E(this, hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice));
-    } else {
-      *out = nullptr;
-    }
-    arena_off += bytes;
-    return 0;
-  }
-  bool skip_host_weights() const { return wmode == W_MEASURE || wmode == W_ATTACH; }
-};
-
-thread_local bool dsm_engine::capturing = false;
-thread_local std::shared_lock<std::shared_mutex>* dsm_engine::api_held = nullptr;
-
-// The library's whole environment: ten DSM_* variables (include/dsm.h lists them), read once per engine by create_impl and
-// tts_create_impl after dot_mode is set.  dsm_env_int is the only getenv in csrc/; the two group counts (DSM_LM_GROUPS,
-// DSM_TTS_GROUPS) go through it where they are computed.
-static int dsm_env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-static void dsm_read_env(dsm_engine* e, bool stt) {
-  // dot_mode 1, STT engine only: the bx3 loop is cheaper per tile, so whole-K workgroups pay from 192 (n, m) tiles on (r03 sweep,
-  // profiles/r03/experiments/chunk_loop_min_mode1.txt: B = 400 13.2 -> 12.0 ms, B = 1024 27.9 -> 26.7), and the bf16 GEMMs leave
-  // the vector ALU to the attention waves, so large attention launches run three workgroups per CU (r03: 52.1 -> 50.4 ms at
-  // B = 2048, 59.8 -> 56.9 at 2304; four: 53.7).  The TTS engine has always kept 384 and 60000 in both modes (it never ran
-  // these two lines); the difference is kept on purpose: dropping it would change which kernels a TTS step launches.
-  if (stt && e->dot_mode == 1) {
-    e->chunk_loop_min_tiles = 192;
-    e->attn_lds_pad = 40000;
-  }
-  e->use_graphs = dsm_env_int("DSM_GRAPHS", 1) != 0;
-  e->fuse_qkv = dsm_env_int("DSM_FUSE_QKV", 1) != 0;
-  e->stream_prio = dsm_env_int("DSM_STREAM_PRIO", 0) != 0;  // the TTS engine's two streams have no priorities: ignored there
-  e->fuse_front = dsm_env_int("DSM_FUSE_FRONT", 0) != 0;
-  e->chunk_loop_min_tiles = dsm_env_int("DSM_CHUNK_LOOP_MIN", e->chunk_loop_min_tiles);
-  e->loop_depth = dsm_env_int("DSM_LOOP_DEPTH", 4) == 2 ? 2 : 4;
-  e->smallk_min_tiles = dsm_env_int("DSM_SMALLK_MIN", e->smallk_min_tiles);
-  const int mt = dsm_env_int("DSM_SMALLK_MT", e->smallk_mt);
-  if (mt == 1 || mt == 2 || mt == 4) e->smallk_mt = mt;
-}
-
-// shared side of dsm_engine::api_mu for the length of one API call: EVERY entry point that issues HIP work holds it (r03;
-// r02 had it on the two ticket entry points only, and the synchronous pair dsm_mimi_encode_step || dsm_asr_step_tokens of
-// tests/harness ran unprotected).  Nested entry points (one public call inside another on the same thread) share the outer hold.
-struct ApiShared {
-  std::shared_lock<std::shared_mutex> lk;
-  bool outer;
-  explicit ApiShared(dsm_engine* e) : outer(dsm_engine::api_held == nullptr) {
-    if (outer) {
-      lk = std::shared_lock<std::shared_mutex>(e->api_mu);
-      dsm_engine::api_held = &lk;
-    }
-  }
-  ~ApiShared() { if (outer) dsm_engine::api_held = nullptr; }
-};
-// exclusive side, for a capture: gives up this thread's shared hold first (two threads upgrading at once would deadlock)
-struct ApiExclusive {
-  std::shared_lock<std::shared_mutex>* held;
-  std::unique_lock<std::shared_mutex> lk;
-  explicit ApiExclusive(dsm_engine* e) : held(dsm_engine::api_held) {
-    if (held) held->unlock();
-    lk = std::unique_lock<std::shared_mutex>(e->api_mu);
-  }
-  ~ApiExclusive() {
-    lk.unlock();
-    if (held) held->lock();
-  }
 };
 
 // ----------------------------------------------------------------------------------------------
@@ -513,7 +290,7 @@ struct ApiExclusive {
 namespace {
 
 struct Loader {
-  dsm_engine* e;
+  DsmDevice* e;
   dsm_st_file* f;
   bool failed = false;
   std::vector<float> get(int64_t numel, const char* fmt, ...) __attribute__((format(printf, 3, 4))) {
@@ -537,12 +314,12 @@ struct Loader {
     va_start(ap, fmt);
     vsnprintf(name, sizeof name, fmt, ap);
     va_end(ap);
-    if (e->wmode == dsm_engine::W_ATTACH) {  // no checkpoint on this rank: replay the loading rank's answers, in order
+    if (e->wmode == DsmDevice::W_ATTACH) {  // no checkpoint on this rank: replay the loading rank's answers, in order
       if (e->manifest_pos >= e->manifest.size()) { failed = true; e->set_error("weight manifest exhausted"); return false; }
       return e->manifest[e->manifest_pos++] != 0;
     }
     const bool found = dsm_st_find(f, name) != nullptr;
-    if (e->wmode == dsm_engine::W_LOAD) e->manifest.push_back(found ? 1 : 0);
+    if (e->wmode == DsmDevice::W_LOAD) e->manifest.push_back(found ? 1 : 0);
     return found;
   }
 };
@@ -556,7 +333,7 @@ int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // lines 4 KB apart, and a wave's chunk is 8 KB of one DRAM page run (experiments/gemm_wk_probe: QKV / gate launches -10 %).
 // split_row: a row offset the kernels address as a tile origin (the gate's up half at +hidden): must be a multiple of 16, else
 // the matrix stays row-major.  The layout depends on the configuration alone, so every rank that attaches to an arena agrees on it.
-int pack_linear(dsm_engine* e, Linear* L, const float* w, int N, int K, bool bf16, const float* bias, int split_row = 0) {
+int pack_linear(DsmDevice* e, Linear* L, const float* w, int N, int K, bool bf16, const float* bias, int split_row = 0) {
   L->packed = bf16 && (split_row % 16 == 0);
   L->N = N;
   L->K = K;
@@ -609,7 +386,7 @@ std::vector<float> load_conv_weight(Loader& ld, const char* prefix, int out_c, i
   return v;
 }
 
-int load_conv(dsm_engine* e, Loader& ld, ConvGeom* c, const char* prefix, int in_c, int out_c, int k, int stride,
+int load_conv(DsmDevice* e, Loader& ld, ConvGeom* c, const char* prefix, int in_c, int out_c, int k, int stride,
               bool bias, bool replicate, const char* wkey = nullptr) {
   char p[256];
   if (wkey)
@@ -638,7 +415,7 @@ int gating_hidden(const dsm_transformer_config& c) {  // core/batched_transforme
   return c.dim_feedforward == 4 * c.d_model ? 11 * c.d_model / 4 : 2 * c.dim_feedforward / 3;
 }
 
-int load_transformer(dsm_engine* e, Loader& ld, TransformerW* t, const dsm_transformer_config& cfg,
+int load_transformer(DsmDevice* e, Loader& ld, TransformerW* t, const dsm_transformer_config& cfg,
                      const char* prefix, bool bf16) {
   t->cfg = cfg;
   const int d = cfg.d_model, hd = d / cfg.num_heads;
@@ -704,7 +481,45 @@ int load_transformer(dsm_engine* e, Loader& ld, TransformerW* t, const dsm_trans
   return 0;
 }
 
-int alloc_transformer_state(dsm_engine* e, TransformerState* st, const dsm_transformer_config& cfg, int B, int T,
+int check_transformer_config(DsmDevice* e, const dsm_transformer_config& t) {
+  if (t.d_model % t.num_heads || t.d_model % 32 || t.d_model > 4096) {
+    e->set_error("d_model must be a multiple of num_heads and of 32, and <= 4096 (the row-norm kernels keep a row in registers)");
+    return DSM_ERR_INVALID;
+  }
+  const int hd = t.d_model / t.num_heads;
+  if (hd != 32 && hd != 64 && hd != 128) { e->set_error("head_dim %d unsupported (32, 64, 128)", hd); return DSM_ERR_INVALID; }
+  return 0;
+}
+
+// The LM trunk both engines share (srv/batched_asr.rs:738-745, srv/tts.rs:345): bf16 text and audio embedding tables, the
+// transformer, out_norm, text_linear — in this order, which is the STT weight arena's carve order.  Cfg: dsm_asr_config or
+// dsm_tts_config (same field names).
+template <typename Cfg>
+int load_lm_trunk(DsmDevice* e, Loader& ld, LmW* w, const Cfg& c) {
+  const int d = c.lm.d_model;
+  const bool skip = e->skip_host_weights();
+  auto te = ld.get((int64_t)c.text_in_vocab_size * d, "text_emb.weight");
+  if (ld.failed) return DSM_ERR_IO;
+  std::vector<uint16_t> tb(skip ? 0 : te.size());
+  for (size_t i = 0; i < tb.size(); ++i) tb[i] = dsm_f32_to_bf16(te[i]);
+  if (int rc = e->upload_w(&w->text_emb, tb.data(), te.size())) return rc;
+  const size_t per = (size_t)c.audio_vocab_size * d;
+  std::vector<uint16_t> ab(skip ? 0 : (size_t)c.audio_codebooks * per);
+  for (int i = 0; i < c.audio_codebooks && !ld.failed && !skip; ++i) {
+    auto ae = ld.get((int64_t)per, "emb.%d.weight", i);
+    for (size_t j = 0; j < ae.size(); ++j) ab[(size_t)i * per + j] = dsm_f32_to_bf16(ae[j]);
+  }
+  if (ld.failed) return DSM_ERR_IO;
+  if (int rc = e->upload_w(&w->audio_emb, ab.data(), (size_t)c.audio_codebooks * per)) return rc;
+  if (int rc = load_transformer(e, ld, &w->tr, c.lm, "transformer", true)) return rc;
+  auto on = ld.get(d, "out_norm.alpha");
+  auto tl = ld.get((int64_t)c.text_out_vocab_size * d, "text_linear.weight");
+  if (ld.failed) return DSM_ERR_IO;
+  if (int rc = e->upload_w(&w->out_norm, on.data(), on.size())) return rc;
+  return pack_linear(e, &w->text_linear, tl.data(), c.text_out_vocab_size, d, true, nullptr);
+}
+
+int alloc_transformer_state(DsmDevice* e, TransformerState* st, const dsm_transformer_config& cfg, int B, int T,
                             bool kv_bf16) {
   const int H = cfg.num_heads, hd = cfg.d_model / H;
   size_t per = (size_t)B * H * cfg.context * hd;
@@ -733,7 +548,36 @@ int alloc_transformer_state(dsm_engine* e, TransformerState* st, const dsm_trans
   return 0;
 }
 
-int load_rvq(dsm_engine* e, Loader& ld, RvqW* r, const char* prefix, int n_q, const dsm_mimi_config& m) {
+int alloc_act(DsmDevice* e, ActScratch* a, size_t rows, int d, int hid) {
+  for (float** p : {&a->x, &a->xn, &a->q, &a->att})
+    if (int rc = e->dalloc(p, rows * d)) return rc;
+  return e->dalloc(&a->g, rows * hid);
+}
+
+// A stream group's view of per-row state: every per-row pointer advanced to row r0 (T = 1).
+void offset_rings(std::vector<void*>& k, std::vector<void*>& v, size_t bytes) {
+  for (size_t l = 0; l < k.size(); ++l) {
+    k[l] = (char*)k[l] + bytes;
+    v[l] = (char*)v[l] + bytes;
+  }
+}
+TransformerState group_view(const TransformerState& full, const dsm_transformer_config& tc, size_t kv_elem_bytes, int r0) {
+  TransformerState v = full;
+  const int hd = tc.d_model / tc.num_heads;
+  offset_rings(v.k, v.v, (size_t)r0 * tc.d_model * tc.context * kv_elem_bytes);  // [rows][H][ctx][hd]
+  v.pos += r0; v.idx += r0; v.start_pos += r0; v.widx += r0;
+  v.rope_cs += (size_t)r0 * hd;
+  return v;
+}
+CaState group_view(const CaState& full, int d_model, size_t kv_elem_bytes, int r0) {
+  CaState v = full;
+  offset_rings(v.k, v.v, (size_t)r0 * d_model * full.smax * kv_elem_bytes);  // [rows][H][smax][hd]
+  v.last += r0; v.act += r0;
+  v.att += (size_t)r0 * d_model;
+  return v;
+}
+
+int load_rvq(DsmDevice* e, Loader& ld, RvqW* r, const char* prefix, int n_q, const dsm_mimi_config& m) {
   const int bins = m.quantizer_bins, dim = m.quantizer_dim;
   r->n_q = n_q;
   auto ip = ld.get((int64_t)dim * m.dimension, "%s.input_proj.weight", prefix);
@@ -765,7 +609,7 @@ int load_rvq(dsm_engine* e, Loader& ld, RvqW* r, const char* prefix, int n_q, co
   return 0;
 }
 
-int load_mimi(dsm_engine* e, Loader& ld, MimiW* m, const dsm_mimi_config& cfg) {
+int load_mimi(DsmDevice* e, Loader& ld, MimiW* m, const dsm_mimi_config& cfg) {
   m->cfg = cfg;
   char p[128];
   int mult = 1, idx = 0, T = DSM_FRAME_SIZE;
@@ -889,17 +733,17 @@ int load_mimi(dsm_engine* e, Loader& ld, MimiW* m, const dsm_mimi_config& cfg) {
     std::vector<const float*> ptrs;
     ptrs.push_back(reinterpret_cast<const float*>(m->rvq_first.codebooks[0].w));
     for (auto& cb : m->rvq_rest.codebooks) ptrs.push_back(reinterpret_cast<const float*>(cb.w));
-    if (e->wmode != dsm_engine::W_MEASURE)  // a table of device pointers: per engine, never part of the arena
+    if (e->wmode != DsmDevice::W_MEASURE)  // a table of device pointers: per engine, never part of the arena
       if (int rc = e->upload(&m->emb_ptrs, ptrs.data(), ptrs.size())) return rc;
   }
   return 0;
 }
 
-int alloc_cat(dsm_engine* e, float** out, const ConvGeom& c, int B) {
+int alloc_cat(DsmDevice* e, float** out, const ConvGeom& c, int B) {
   return e->dalloc(out, (size_t)B * (c.S + c.T_in) * c.in_c);
 }
 
-void add_desc(MimiState* s, float* cat, const ConvGeom& c) {
+void add_desc(std::vector<ConvStateDesc>& descs, float* cat, const ConvGeom& c) {  // a conv that carries frames between steps
   if (c.S == 0) return;
   ConvStateDesc d;
   d.cat = cat;
@@ -908,13 +752,13 @@ void add_desc(MimiState* s, float* cat, const ConvGeom& c) {
   d.T = c.T_in;
   d.C = c.in_c;
   d.replicate = c.replicate ? 1 : 0;
-  s->h_descs.push_back(d);
+  descs.push_back(d);
 }
 
-int alloc_mimi_state(dsm_engine* e, MimiState* s, const MimiW& w, int B) {
+int alloc_mimi_state(DsmDevice* e, MimiState* s, const MimiW& w, int B) {
   const dsm_mimi_config& cfg = w.cfg;
   if (int rc = alloc_cat(e, &s->cat_init, w.init_conv, B)) return rc;
-  add_desc(s, s->cat_init, w.init_conv);
+  add_desc(s->h_descs, s->cat_init, w.init_conv);
   s->stages.resize(w.stages.size());
   for (size_t i = 0; i < w.stages.size(); ++i) {
     const MimiW::Stage& st = w.stages[i];
@@ -922,12 +766,12 @@ int alloc_mimi_state(dsm_engine* e, MimiState* s, const MimiW& w, int B) {
     if (int rc = alloc_cat(e, &s->stages[i].cat_ra, st.ra, B)) return rc;
     if (int rc = alloc_cat(e, &s->stages[i].cat_rb, st.rb, B)) return rc;
     if (int rc = alloc_cat(e, &s->stages[i].cat_down, st.down, B)) return rc;
-    add_desc(s, s->stages[i].cat_ra, st.ra);
-    add_desc(s, s->stages[i].cat_rb, st.rb);
-    add_desc(s, s->stages[i].cat_down, st.down);
+    add_desc(s->h_descs, s->stages[i].cat_ra, st.ra);
+    add_desc(s->h_descs, s->stages[i].cat_rb, st.rb);
+    add_desc(s->h_descs, s->stages[i].cat_down, st.down);
   }
   if (int rc = alloc_cat(e, &s->cat_final, w.final_conv, B)) return rc;
-  add_desc(s, s->cat_final, w.final_conv);
+  add_desc(s->h_descs, s->cat_final, w.final_conv);
   const int Tt = w.final_conv.T_out, d = cfg.dimension;
   if (int rc = e->dalloc(&s->x_tr, (size_t)B * Tt * d)) return rc;
   if (int rc = e->dalloc(&s->xn, (size_t)B * Tt * d)) return rc;
@@ -936,7 +780,7 @@ int alloc_mimi_state(dsm_engine* e, MimiState* s, const MimiW& w, int B) {
   if (int rc = e->dalloc(&s->ff, (size_t)B * Tt * cfg.transformer.dim_feedforward)) return rc;
   if (int rc = alloc_cat(e, &s->cat_ds, w.downsample, B)) return rc;
   s->ds_desc = (int)s->h_descs.size();
-  add_desc(s, s->cat_ds, w.downsample);
+  add_desc(s->h_descs, s->cat_ds, w.downsample);
   if (int rc = e->dalloc(&s->latent, (size_t)B * d)) return rc;
   if (int rc = e->dalloc(&s->res_first, (size_t)B * cfg.quantizer_dim)) return rc;
   if (int rc = e->dalloc(&s->res_rest, (size_t)B * cfg.quantizer_dim)) return rc;
@@ -955,7 +799,7 @@ int alloc_mimi_state(dsm_engine* e, MimiState* s, const MimiW& w, int B) {
 // GEMM launch
 // ----------------------------------------------------------------------------------------------
 // whole-K-in-the-workgroup GEMMs (dsm_gemm_wk.h): dot_mode 1, bf16 weights, at most four K-chunks, M <= 64
-bool wk_applicable(const dsm_engine* e, bool bf16_weights, int Kpad, int K, int M) {
+bool wk_applicable(const DsmDevice* e, bool bf16_weights, int Kpad, int K, int M) {
   const int chunks = (Kpad + DSM_KC - 1) / DSM_KC;
   return bf16_weights && e->dot_mode == 1 && K % 32 == 0 && Kpad == K && chunks <= 4 && M <= 64;
 }
@@ -979,7 +823,7 @@ void launch_tile(hipStream_t st, dim3 grid, const GemmArgs& a, bool bx3, bool ro
 }
 
 template <typename WT, typename KVT, int EPI, int NT>
-int launch_gemm_tiled(dsm_engine* e, hipStream_t st, GemmArgs& a) {
+int launch_gemm_tiled(DsmDevice* e, hipStream_t st, GemmArgs& a) {
   int chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
   const int gx = (a.N + 63) / 64;
   const bool bx3 = e->dot_mode == 1 && sizeof(WT) == 2;  // dot_mode 1: every bf16-weight GEMM on the bf16 matrix pipe
@@ -1089,7 +933,7 @@ int launch_gemm_tiled(dsm_engine* e, hipStream_t st, GemmArgs& a) {
 }
 
 template <typename WT, typename KVT, int EPI, int NT>
-int launch_gemm_t(dsm_engine* e, hipStream_t st, GemmArgs& a, bool aligned) {
+int launch_gemm_t(DsmDevice* e, hipStream_t st, GemmArgs& a, bool aligned) {
   if (aligned && a.K % 32 == 0) return launch_gemm_tiled<WT, KVT, EPI, NT>(e, st, a);
   const int chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
   const int rounds = (chunks + 15) / 16;          // chunks per wave when there are more than 16
@@ -1142,7 +986,7 @@ int launch_gemm_t(dsm_engine* e, hipStream_t st, GemmArgs& a, bool aligned) {
 // hipGraph and replay that from then on.  key: everything the body's launch arguments depend on that may change between
 // calls (caller-supplied pointers, branch selectors).
 template <typename F>
-int run_captured(dsm_engine* e, dsm_engine::GraphSlot& gs, hipStream_t st, uint64_t key, F&& body) {
+int run_captured(DsmDevice* e, DsmDevice::GraphSlot& gs, hipStream_t st, uint64_t key, F&& body) {
   if (!e->use_graphs || e->prof_mask != 0 || gs.disabled) { e->eager_bodies += 1; return body(); }
   if (gs.exec && gs.key == key && gs.ws_gen == e->ws_gen) {
     HIPCHK(hipGraphLaunch(gs.exec, st));
@@ -1168,7 +1012,7 @@ int run_captured(dsm_engine* e, dsm_engine::GraphSlot& gs, hipStream_t st, uint6
   if (hb != hipSuccess) {
     (void)hipGetLastError();
     e->note_capture_failure("hipStreamBeginCapture", hb);
-    if (++gs.failures >= dsm_engine::kMaxCaptureTries) gs.disabled = true;
+    if (++gs.failures >= DsmDevice::kMaxCaptureTries) gs.disabled = true;
     gs.warm = 0;
     e->eager_bodies += 1;
     return body();
@@ -1191,7 +1035,7 @@ int run_captured(dsm_engine* e, dsm_engine::GraphSlot& gs, hipStream_t st, uint6
     e->note_capture_failure(rc ? (e->capture_failed ? "workspace grew during capture" : "launch error during capture")
                                : he != hipSuccess ? "hipStreamEndCapture" : !g ? "hipStreamEndCapture returned no graph" : "hipGraphInstantiate",
                             rc ? hipSuccess : he != hipSuccess ? he : hi);
-    if (++gs.failures >= dsm_engine::kMaxCaptureTries) gs.disabled = true;
+    if (++gs.failures >= DsmDevice::kMaxCaptureTries) gs.disabled = true;
     gs.warm = 0;
     e->eager_bodies += 1;
     return body();
@@ -1217,6 +1061,9 @@ RowMap batch_map(long bstride, int rpb, int ld, int toff) {
   r.toff = toff;
   return r;
 }
+RowMap cat_map(const ConvGeom& consumer) {  // rows (b, t) -> the consumer's concat buffer, after its carried frames
+  return batch_map((long)(consumer.S + consumer.T_in) * consumer.in_c, consumer.T_in, consumer.in_c, consumer.S);
+}
 
 GemmArgs base_args(const Linear& L, const float* X, RowMap xmap, int M) {
   GemmArgs a;
@@ -1235,13 +1082,13 @@ GemmArgs base_args(const Linear& L, const float* X, RowMap xmap, int M) {
 }
 
 template <typename WT>
-int gemm_store(dsm_engine* e, hipStream_t st, GemmArgs& a, bool aligned = true) {
+int gemm_store(DsmDevice* e, hipStream_t st, GemmArgs& a, bool aligned = true) {
   return launch_gemm_t<WT, float, EPI_STORE, 1>(e, st, a, aligned);
 }
 
 // conv as a GEMM over the consumer's concat buffer; output goes to Y (raw) and/or Y2 (ELU copy, usually the
 // next conv's concat buffer at time offset S_next)
-int run_conv(dsm_engine* e, hipStream_t st, const ConvGeom& c, const float* cat, int B, float* y, RowMap ymap,
+int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, int B, float* y, RowMap ymap,
              float* y2, RowMap y2map, const float* res, RowMap rmap) {
   const long bstride = (long)(c.S + c.T_in) * c.in_c;
   GemmArgs a = base_args(c.lin, cat, batch_map(bstride, c.T_out, c.stride * c.in_c, 0), B * c.T_out);

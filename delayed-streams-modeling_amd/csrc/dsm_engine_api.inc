@@ -3,7 +3,7 @@
 namespace {
 
 template <typename KVT, int HD, int T>
-int launch_attn_t(dsm_engine* e, hipStream_t st, float* out, const float* q, const void* k, const void* v,
+int launch_attn_t(DsmDevice* e, hipStream_t st, float* out, const float* q, const void* k, const void* v,
                   const uint32_t* start_pos, const uint8_t* active, int B, int H, int ctx, int d, const AttnFused& fq) {
   // bf16 rings: eight keys per lane group and batch at head_dim 128 (126 VGPRs; 0.69 of the HBM peak alone at 32 slots, 0.88 at 1024),
   // four below (78 VGPRs: stt-2.6b's head_dim-64 launches 39.2 against 42.8 us).  Four at head_dim 128 buys the B = 64 step 0.6 %
@@ -42,7 +42,7 @@ int launch_attn_t(dsm_engine* e, hipStream_t st, float* out, const float* q, con
 }
 
 template <typename KVT>
-int launch_attn(dsm_engine* e, hipStream_t st, float* out, const float* q, const void* k, const void* v,
+int launch_attn(DsmDevice* e, hipStream_t st, float* out, const float* q, const void* k, const void* v,
                 const uint32_t* start_pos, const uint8_t* active, int B, int H, int hd, int T, int ctx, int d,
                 const AttnFused& fq) {
 #define DSM_ATTN(HDv, Tv) \
@@ -53,7 +53,7 @@ int launch_attn(dsm_engine* e, hipStream_t st, float* out, const float* q, const
   return DSM_ERR_INVALID;
 }
 
-int run_norm(dsm_engine* e, hipStream_t st, float* y, const float* x, const float* w, const float* b, int rows, int d,
+int run_norm(DsmDevice* e, hipStream_t st, float* y, const float* x, const float* w, const float* b, int rows, int d,
              int rms) {
   hipLaunchKernelGGL(row_norm_kernel, dim3(rows), dim3(256), 0, st, y, x, w, b, rows, d,
                      rms ? 1e-8f : 1e-5f, rms);
@@ -68,7 +68,7 @@ int run_norm(dsm_engine* e, hipStream_t st, float* y, const float* x, const floa
 // phase: 0 = the whole stack; 1 = only the head of it — ring bookkeeping, first norm, layer 0's QKV projection and attention
 // (what a stream group runs before it lets the next group start: the staggered start of lm_step); 2 = everything after that.
 template <typename WT, typename KVT>
-int transformer_forward(dsm_engine* e, hipStream_t st, const TransformerW& w, TransformerState& s, float* x, float* xn,
+int transformer_forward(DsmDevice* e, hipStream_t st, const TransformerW& w, TransformerState& s, float* x, float* xn,
                         float* q, float* att, float* ff, int B, int T, const uint8_t* d_mask, float* final_out,
                         RowMap final_map, const float* post_norm_w = nullptr, float* post_norm_out = nullptr, int phase = 0,
                         const CaState* ca = nullptr, bool head_done = false) {
@@ -185,10 +185,40 @@ int transformer_forward(dsm_engine* e, hipStream_t st, const TransformerW& w, Tr
   return 0;
 }
 
+// The ring element type of an LM as a template argument: f(uint16_t{}) for bf16 rings (kv_bf16), f(float{}) for f32 ones.
+template <typename F>
+int with_kv_type(bool kv_bf16, F&& f) {
+  return kv_bf16 ? f(uint16_t{}) : f(float{});
+}
+
+// Stream groups: group 0 runs on `st` (the model stream), group g > 0 on s_grp[g].  fork_groups lets the group streams start
+// behind what `st` holds so far; run_groups launches body(g, stream) for the trailing groups first — `st` is the stream later
+// work queues behind — and records each group's "done" event; join_groups makes `st` wait for them.
+int fork_groups(DsmDevice* e, hipStream_t st, size_t G) {
+  if (G > 1) {
+    HIPCHK(hipEventRecord(e->ev_fork, st));
+    for (size_t g = 1; g < G; ++g) HIPCHK(hipStreamWaitEvent(e->s_grp[g], e->ev_fork, 0));
+  }
+  return 0;
+}
+template <typename F>
+int run_groups(DsmDevice* e, hipStream_t st, size_t G, bool serialize, F&& body) {
+  for (size_t g = G; g-- > 0;) {
+    hipStream_t gs = (g == 0 || serialize) ? st : e->s_grp[g];
+    if (int rc = body(g, gs)) return rc;
+    if (g > 0) HIPCHK(hipEventRecord(e->ev_grp_done[g], gs));
+  }
+  return 0;
+}
+int join_groups(DsmDevice* e, hipStream_t st, size_t G) {
+  for (size_t g = 1; g < G; ++g) HIPCHK(hipStreamWaitEvent(st, e->ev_grp_done[g], 0));
+  return 0;
+}
+
 int mimi_encode_body(dsm_engine* e, int side, hipStream_t st);
 // Mimi::encode_step — core/mimi.rs:195-206.  PCM already sits in cat_init[:, S:, :], mask in s.mask.
 int mimi_encode(dsm_engine* e, int side, hipStream_t st) {
-  return run_captured(e, e->g_enc[side], st, (uint64_t)e->sid(st), [&] { return mimi_encode_body(e, side, st); });
+  return run_captured(e, *e->g_enc[side], st, (uint64_t)e->sid(st), [&] { return mimi_encode_body(e, side, st); });
 }
 int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
   const MimiW& w = e->mimi_w;
@@ -197,9 +227,6 @@ int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
   const RowMap none = plain_map(1, 1);
   e->tag_gemm[e->sid(st)] = DSM_PROF_GEMM_MIMI;
   e->tag_attn[e->sid(st)] = DSM_PROF_ATTN_MIMI;
-  auto cat_map = [&](const ConvGeom& consumer) {  // rows (b,t) -> consumer's concat buffer, after its carried frames
-    return batch_map((long)(consumer.S + consumer.T_in) * consumer.in_c, consumer.T_in, consumer.in_c, consumer.S);
-  };
   // SeaNetEncoder::step — core/seanet.rs:292-302
   // The real Mimi front end (1 -> 64 k 7, residual block 64 -> 32 k 3 -> 64 k 1, f32, frames a multiple of 64) runs as one
   // kernel whose intermediates stay in LDS (seanet_front_kernel); any other geometry takes the three GEMM launches.
@@ -297,11 +324,10 @@ int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
 }
 
 // ---- decode side ---------------------------------------------------------------------------------------
-int alloc_dec_state(dsm_engine* e) {
-  MimiDecState& s = e->dec;
-  const MimiW& w = e->mimi_w;
+int alloc_dec_state(DsmDevice* e, const MimiW& w, MimiDecState& s, int B) {  // on first use
+  if (s.ready) return 0;
   const dsm_mimi_config& c = w.cfg;
-  const int B = e->B, dim = c.dimension, T2 = w.dec_init.T_in;
+  const int dim = c.dimension, T2 = w.dec_init.T_in;
   if (!w.has_decoder) {
     e->set_error("the Mimi checkpoint has no decoder.* tensors: decode_step is unavailable");
     return DSM_ERR_STATE;
@@ -318,12 +344,7 @@ int alloc_dec_state(dsm_engine* e) {
   if (int rc = e->dalloc(&s.att, (size_t)B * T2 * dim)) return rc;
   if (int rc = e->dalloc(&s.ff, (size_t)B * T2 * c.transformer.dim_feedforward)) return rc;
   if (int rc = alloc_transformer_state(e, &s.tr, c.transformer, B, T2, false)) return rc;
-  auto add = [&](float* cat, const ConvGeom& g) {
-    if (g.S == 0) return;
-    ConvStateDesc d;
-    d.cat = cat; d.bstride = (long)(g.S + g.T_in) * g.in_c; d.S = g.S; d.T = g.T_in; d.C = g.in_c; d.replicate = 0;
-    s.h_descs.push_back(d);
-  };
+  auto add = [&](float* cat, const ConvGeom& g) { add_desc(s.h_descs, cat, g); };  // (no decoder conv pads by replication)
   if (int rc = alloc_cat(e, &s.cat_init, w.dec_init, B)) return rc;
   add(s.cat_init, w.dec_init);
   s.stages.resize(w.dec_stages.size());
@@ -344,27 +365,23 @@ int alloc_dec_state(dsm_engine* e) {
   add(s.cat_final, w.dec_final);
   if (int rc = e->dalloc(&s.pcm, (size_t)B * DSM_FRAME_SIZE * c.channels)) return rc;
   if (int rc = e->upload(&s.descs, s.h_descs.data(), s.h_descs.size())) return rc;
-  HIPCHK(hipHostMalloc((void**)&e->h_pcm_out, sizeof(float) * (size_t)B * DSM_FRAME_SIZE));
+  if (int rc = e->halloc(&s.h_pcm_out, (size_t)B * DSM_FRAME_SIZE)) return rc;
+  s.graph = e->graph_slot();
   s.ready = true;
   return 0;
 }
 
-int mimi_decode_body(dsm_engine* e, hipStream_t st);
+int mimi_decode_body(DsmDevice* e, const MimiW& w, MimiDecState& s, int B, hipStream_t st);
 // Mimi::decode_step — core/mimi.rs:217-225.  codes in s.codes, mask in s.mask; PCM lands in s.pcm.
-int mimi_decode(dsm_engine* e, hipStream_t st) {
-  return run_captured(e, e->g_dec, st, (uint64_t)e->sid(st), [&] { return mimi_decode_body(e, st); });
+int mimi_decode(DsmDevice* e, const MimiW& w, MimiDecState& s, int B, hipStream_t st) {
+  return run_captured(e, *s.graph, st, (uint64_t)e->sid(st), [&] { return mimi_decode_body(e, w, s, B, st); });
 }
-int mimi_decode_body(dsm_engine* e, hipStream_t st) {
-  const MimiW& w = e->mimi_w;
-  MimiDecState& s = e->dec;
+int mimi_decode_body(DsmDevice* e, const MimiW& w, MimiDecState& s, int B, hipStream_t st) {
   const dsm_mimi_config& c = w.cfg;
-  const int B = e->B, dim = c.dimension, qd = c.quantizer_dim, T2 = w.dec_init.T_in;
+  const int dim = c.dimension, qd = c.quantizer_dim, T2 = w.dec_init.T_in;
   const RowMap none = plain_map(1, 1);
   e->tag_gemm[e->sid(st)] = DSM_PROF_GEMM_MIMI;
   e->tag_attn[e->sid(st)] = DSM_PROF_ATTN_MIMI;
-  auto cat_map = [&](const ConvGeom& consumer) {
-    return batch_map((long)(consumer.S + consumer.T_in) * consumer.in_c, consumer.T_in, consumer.in_c, consumer.S);
-  };
   // SplitResidualVectorQuantizer::decode — core/quantization.rs:380-390
   {
     RvqGatherArgs g;
@@ -449,17 +466,12 @@ int lm_group_body(dsm_engine* e, hipStream_t st, int g, uint32_t* d_text_out, fl
   e->tag_gemm[e->sid(st)] = DSM_PROF_GEMM_LM;
   e->tag_attn[e->sid(st)] = DSM_PROF_ATTN_LM;
   uint8_t* gmask = s.gmask + b0;
-  float* x = s.x + (size_t)b0 * d;
-  const int hid = w.tr.hidden;
-  float *xn = s.xn + (size_t)b0 * d, *q = s.q + (size_t)b0 * d, *att = s.att + (size_t)b0 * d, *gg = s.g + (size_t)b0 * hid;
+  const ActScratch sc = s.act.from_row(b0, d, w.tr.hidden);
   float* hidden = s.hidden + (size_t)b0 * d;
-  int rc;
-  if (c.kv_bf16)
-    rc = transformer_forward<uint16_t, uint16_t>(e, st, w.tr, grp.view, x, xn, q, att, gg, nb, 1, gmask, nullptr,
-                                                 plain_map(1, 1), w.out_norm, hidden, phase);
-  else
-    rc = transformer_forward<uint16_t, float>(e, st, w.tr, grp.view, x, xn, q, att, gg, nb, 1, gmask, nullptr,
-                                              plain_map(1, 1), w.out_norm, hidden, phase);
+  int rc = with_kv_type(c.kv_bf16 != 0, [&](auto kv) {
+    return transformer_forward<uint16_t, decltype(kv)>(e, st, w.tr, grp.view, sc.x, sc.xn, sc.q, sc.att, sc.g, nb, 1, gmask, nullptr,
+                                                       plain_map(1, 1), w.out_norm, hidden, phase);
+  });
   if (rc || phase == 1) return rc;  // hidden = out_norm(x) — core/lm.rs:1002 (fused behind the last layer's linear_out)
   float* logits = s.logits + (size_t)b0 * c.text_out_vocab_size;
   {
@@ -497,7 +509,7 @@ int lm_group_head(dsm_engine* e, hipStream_t st, int g, const uint32_t* d_codes,
   const int d = c.lm.d_model, b0 = grp.b0, nb = grp.nb, nc = c.audio_codebooks;
   uint8_t* gmask = s.gmask + b0;
   HIPCHK(hipMemcpyAsync(gmask, d_mask + b0, (size_t)nb, hipMemcpyDeviceToDevice, st));
-  float* x = s.x + (size_t)b0 * d;
+  float* x = s.act.x + (size_t)b0 * d;
   hipLaunchKernelGGL(lm_input_kernel, dim3(nb, (d + 511) / 512), dim3(256), 0, st, x, w.text_emb, w.audio_emb,
                      d_codes + (size_t)b0 * nc, s.next_cb + (size_t)b0 * nc, s.text_token + b0, s.first_step + b0, gmask, nc, d,
                      c.audio_vocab_size, (uint32_t)c.audio_vocab_size - 1, (uint32_t)c.text_in_vocab_size - 1);
@@ -515,7 +527,7 @@ int lm_group_head(dsm_engine* e, hipStream_t st, int g, const uint32_t* d_codes,
 int lm_group_rest(dsm_engine* e, hipStream_t st, int g, uint32_t* d_text_out, float* d_prs_out, bool after_prefix) {
   const uint64_t key = (uint64_t)e->sid(st) ^ ((uint64_t)(uintptr_t)d_text_out << 3) ^ ((uint64_t)(uintptr_t)d_prs_out * 0x9E3779B97F4A7C15ull) ^
                        (after_prefix ? 0x8000000000000000ull : 0ull);
-  return run_captured(e, e->g_grp[g], st, key, [&] { return lm_group_body(e, st, g, d_text_out, d_prs_out, after_prefix ? 2 : 0); });
+  return run_captured(e, *e->g_grp[g], st, key, [&] { return lm_group_body(e, st, g, d_text_out, d_prs_out, after_prefix ? 2 : 0); });
 }
 
 // Before the model stream overwrites anything a group reads at the start of its step (codes, mask), every group must
@@ -526,11 +538,7 @@ int wait_group_inputs(dsm_engine* e) {
   return 0;
 }
 // Model stream waits until every group finished its last step (slot resets, position edits).
-int join_groups(dsm_engine* e) {
-  if (!e->grp_busy) return 0;
-  for (size_t g = 1; g < e->lm.groups.size(); ++g) HIPCHK(hipStreamWaitEvent(e->s_model, e->ev_grp_done[g], 0));
-  return 0;
-}
+int join_groups(dsm_engine* e) { return e->grp_busy ? join_groups(e, e->s_model, e->lm.groups.size()) : 0; }
 
 // One LM step of the whole batch: group 0 on `st` (the model stream), the others forked onto their own streams.
 // Groups are NOT joined at the end of the step: each consumes only its own slots' state, so they free-run and one
@@ -539,10 +547,7 @@ int join_groups(dsm_engine* e) {
 int lm_step(dsm_engine* e, hipStream_t st, const uint32_t* d_codes, const uint8_t* d_mask, uint32_t* d_text_out,
             float* d_prs_out) {
   const size_t G = e->lm.groups.size();
-  if (G > 1) {
-    HIPCHK(hipEventRecord(e->ev_fork, st));
-    for (size_t g = 1; g < G; ++g) HIPCHK(hipStreamWaitEvent(e->s_grp[g], e->ev_fork, 0));
-  }
+  if (int rc = fork_groups(e, st, G)) return rc;
   // Staggered start (r02).  Groups that begin a step together stay in phase through all the layers — their attention
   // launches run against each other (two HBM-bound kernels halving each other's bandwidth: 60 us live against 39 alone at
   // B = 64) and so do their GEMMs — which is the opposite of what the groups are for.  So group g starts only when group
@@ -558,12 +563,9 @@ int lm_step(dsm_engine* e, hipStream_t st, const uint32_t* d_codes, const uint8_
     if (int rc = lm_group_head(e, gs, (int)g, d_codes, d_mask, stagger)) return rc;
     if (stagger && g + 1 < G) HIPCHK(hipEventRecord(e->ev_stagger[g], gs));
   }
-  // the trailing groups first: the model stream (group 0) is the one later work queues behind
-  for (size_t g = G; g-- > 0;) {
-    hipStream_t gs = (g == 0 || e->serialize_groups) ? st : e->s_grp[g];
-    if (int rc = lm_group_rest(e, gs, (int)g, d_text_out, d_prs_out, stagger)) return rc;
-    if (g > 0) HIPCHK(hipEventRecord(e->ev_grp_done[g], gs));
-  }
+  if (int rc = run_groups(e, st, G, e->serialize_groups,
+                          [&](size_t g, hipStream_t gs) { return lm_group_rest(e, gs, (int)g, d_text_out, d_prs_out, stagger); }))
+    return rc;
   if (G > 1) e->grp_busy = true;
   return 0;
 }
@@ -650,10 +652,27 @@ int ensure_model_side_mimi(dsm_engine* e) {
   return 0;
 }
 
-int reset_transformer_slot(dsm_engine* e, hipStream_t st, TransformerState& s, int slot) {
+int reset_transformer_slot(DsmDevice* e, hipStream_t st, TransformerState& s, int slot) {
   HIPCHK(hipMemsetAsync(s.pos + slot, 0, sizeof(uint32_t), st));  // core/kv_cache.rs:111-117
   HIPCHK(hipMemsetAsync(s.idx + slot, 0, sizeof(uint32_t), st));
   return 0;
+}
+
+// One slot of the decode state: conv states, convtr carries and the upsampler's carry zeroed.  fresh: the slot's next frame is
+// the first of a Mimi of its own (the TTS engine: srv/tts.rs:499-500 clone() + reset_state()) — not started, and the decoder
+// transformer back at position 0.
+int reset_decoder_slot(DsmDevice* e, const MimiW& w, MimiDecState& d, hipStream_t st, int slot, bool fresh) {
+  hipLaunchKernelGGL(conv_state_reset_kernel, dim3((unsigned)d.h_descs.size()), dim3(256), 0, st, d.descs, slot);
+  HIPCHK(hipGetLastError());
+  for (size_t i = 0; i < w.dec_stages.size(); ++i) {
+    const size_t n = (size_t)(w.dec_stages[i].k - w.dec_stages[i].stride) * w.dec_stages[i].out_c;
+    HIPCHK(hipMemsetAsync(d.stages[i].carry + (size_t)slot * n, 0, n * sizeof(float), st));
+  }
+  const size_t n = (size_t)w.cfg.downsample_stride * w.cfg.dimension;
+  HIPCHK(hipMemsetAsync(d.up_carry + (size_t)slot * n, 0, n * sizeof(float), st));
+  if (!fresh) return 0;
+  HIPCHK(hipMemsetAsync(d.started + slot, 0, 1, st));
+  return reset_transformer_slot(e, st, d.tr, slot);
 }
 
 int reset_mimi_slot(dsm_engine* e, int side, hipStream_t st, int slot) {  // Mimi::reset_batch_idx — core/mimi.rs:236-244
@@ -664,20 +683,9 @@ int reset_mimi_slot(dsm_engine* e, int side, hipStream_t st, int slot) {  // Mim
     hipLaunchKernelGGL(conv_state_reset_kernel, dim3((unsigned)s.h_descs.size()), dim3(256), 0, st, s.descs, slot);
     HIPCHK(hipGetLastError());
   }
-  if (side == 0 && e->dec.ready) {
-    // decode side of the same Mimi: conv / convtr carries are zeroed, the decoder transformer is NOT reset
-    // (the reference resets encoder_transformer twice instead: core/mimi.rs:237-238)
-    MimiDecState& d = e->dec;
-    hipLaunchKernelGGL(conv_state_reset_kernel, dim3((unsigned)d.h_descs.size()), dim3(256), 0, st, d.descs, slot);
-    const MimiW& w = e->mimi_w;
-    for (size_t i = 0; i < w.dec_stages.size(); ++i) {
-      size_t n = (size_t)(w.dec_stages[i].k - w.dec_stages[i].stride) * w.dec_stages[i].out_c;
-      HIPCHK(hipMemsetAsync(d.stages[i].carry + (size_t)slot * n, 0, n * sizeof(float), st));
-    }
-    size_t n = (size_t)w.cfg.downsample_stride * w.cfg.dimension;
-    HIPCHK(hipMemsetAsync(d.up_carry + (size_t)slot * n, 0, n * sizeof(float), st));
-    HIPCHK(hipGetLastError());
-  }
+  // decode side of the same Mimi: the decoder transformer is NOT reset (the reference resets encoder_transformer twice
+  // instead: core/mimi.rs:237-238)
+  if (side == 0 && e->dec.ready) return reset_decoder_slot(e, e->mimi_w, e->dec, st, slot, false);
   return 0;
 }
 
@@ -723,57 +731,31 @@ void dsm_mimi_config_v0_1(dsm_mimi_config* out, int num_codebooks) { dsm_preset_
 void dsm_asr_config_stt_1b_en_fr(dsm_asr_config* out) { dsm_preset_stt_1b_en_fr(out); }
 void dsm_asr_config_stt_2_6b_en(dsm_asr_config* out) { dsm_preset_stt_2_6b_en(out); }
 
+}  // extern "C" (reopened below)
+
+// The end of every create function: a failed create leaves its message in g_create_error and no engine behind (the context's
+// destructor releases whatever the partial create was handed).
+template <typename E>
+static int finish_create(E* e, int rc, E** out) {
+  if (rc) {
+    g_create_error = e->err;
+    delete e;
+    e = nullptr;
+  }
+  *out = e;
+  return rc;
+}
+
+extern "C" {
+
 const char* dsm_last_error(const dsm_engine* e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 
-void dsm_destroy(dsm_engine* e) {
-  if (!e) return;
-  (void)hipSetDevice(e->device);
-  (void)hipDeviceSynchronize();
-  for (dsm_engine::GraphSlot* gs : {&e->g_enc[0], &e->g_enc[1], &e->g_dec})
-    if (gs->exec) (void)hipGraphExecDestroy(gs->exec);
-  for (auto& pair : e->g_ttsg)
-    for (auto& gs : pair)
-      if (gs.exec) (void)hipGraphExecDestroy(gs.exec);
-  for (auto& gs : e->g_grp)
-    if (gs.exec) (void)hipGraphExecDestroy(gs.exec);
-  for (void* p : e->allocs) (void)hipFree(p);
-  if (e->arena && e->arena_owned) (void)hipFree(e->arena);
-  for (auto& ps : e->pipe) {
-    if (ps.h_pcm) (void)hipHostFree(ps.h_pcm);
-    if (ps.h_mask) (void)hipHostFree(ps.h_mask);
-    if (ps.ev_done) (void)hipEventDestroy(ps.ev_done);
-    if (ps.ev_consumed) (void)hipEventDestroy(ps.ev_consumed);
-  }
-  for (float* p : e->gemm_ws)
-    if (p) (void)hipFree(p);
-  if (e->h_pcm) (void)hipHostFree(e->h_pcm);
-  if (e->h_pcm1) (void)hipHostFree(e->h_pcm1);
-  if (e->h_mask) (void)hipHostFree(e->h_mask);
-  if (e->h_codes) (void)hipHostFree(e->h_codes);
-  if (e->h_text) (void)hipHostFree(e->h_text);
-  if (e->h_prs) (void)hipHostFree(e->h_prs);
-  if (e->h_pcm_out) (void)hipHostFree(e->h_pcm_out);
-  for (hipEvent_t ev : {e->ev_join, e->ev_codes_consumed, e->ev_a, e->ev_b, e->ev_c, e->ev_d})
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& r : e->prof_recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  for (hipEvent_t ev : e->prof_pool) (void)hipEventDestroy(ev);
-  for (int g = 0; g < dsm_engine::kMaxGroups; ++g) {
-    if (e->ev_grp_in[g]) (void)hipEventDestroy(e->ev_grp_in[g]);
-    if (e->ev_grp_done[g]) (void)hipEventDestroy(e->ev_grp_done[g]);
-    if (e->ev_stagger[g]) (void)hipEventDestroy(e->ev_stagger[g]);
-    if (e->s_grp[g]) (void)hipStreamDestroy(e->s_grp[g]);
-  }
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->s_enc) (void)hipStreamDestroy(e->s_enc);
-  if (e->s_model) (void)hipStreamDestroy(e->s_model);
-  delete e;
-}
+void dsm_destroy(dsm_engine* e) { delete e; }  // ~DsmDevice releases what the engine was handed
 
 // Mimi + LM weights through whatever weight mode the engine is in (dsm_engine::WeightMode); lm / mimi are null when attaching
 static int load_all_weights(dsm_engine* e, dsm_st_file* lm, dsm_st_file* mimi) {
   const dsm_asr_config& c = e->cfg;
   const int d = c.lm.d_model;
-  const bool skip = e->skip_host_weights();
   {
     Loader ld{e, mimi};
     int rc = load_mimi(e, ld, &e->mimi_w, c.mimi);
@@ -781,25 +763,7 @@ static int load_all_weights(dsm_engine* e, dsm_st_file* lm, dsm_st_file* mimi) {
     if (ld.failed) return DSM_ERR_IO;
   }
   Loader ld{e, lm};
-  auto te = ld.get((int64_t)c.text_in_vocab_size * d, "text_emb.weight");
-  if (ld.failed) return DSM_ERR_IO;
-  std::vector<uint16_t> tb(skip ? 0 : te.size());
-  for (size_t i = 0; i < tb.size(); ++i) tb[i] = dsm_f32_to_bf16(te[i]);
-  if (int rc = e->upload_w(&e->lm_w.text_emb, tb.data(), te.size())) return rc;
-  const size_t per = (size_t)c.audio_vocab_size * d;
-  std::vector<uint16_t> ab(skip ? 0 : (size_t)c.audio_codebooks * per);
-  for (int i = 0; i < c.audio_codebooks && !ld.failed && !skip; ++i) {
-    auto ae = ld.get((int64_t)per, "emb.%d.weight", i);
-    for (size_t j = 0; j < ae.size(); ++j) ab[(size_t)i * per + j] = dsm_f32_to_bf16(ae[j]);
-  }
-  if (ld.failed) return DSM_ERR_IO;
-  if (int rc = e->upload_w(&e->lm_w.audio_emb, ab.data(), (size_t)c.audio_codebooks * per)) return rc;
-  if (int rc = load_transformer(e, ld, &e->lm_w.tr, c.lm, "transformer", true)) return rc;
-  auto on = ld.get(d, "out_norm.alpha");
-  auto tl = ld.get((int64_t)c.text_out_vocab_size * d, "text_linear.weight");
-  if (ld.failed) return DSM_ERR_IO;
-  if (int rc = e->upload_w(&e->lm_w.out_norm, on.data(), on.size())) return rc;
-  if (int rc = pack_linear(e, &e->lm_w.text_linear, tl.data(), c.text_out_vocab_size, d, true, nullptr)) return rc;
+  if (int rc = load_lm_trunk(e, ld, &e->lm_w, c)) return rc;
   if (c.extra_heads_num > 0) {
     std::vector<float> eh((size_t)c.extra_heads_num * c.extra_heads_dim * d);
     for (int i = 0; i < c.extra_heads_num && !ld.failed; ++i) {
@@ -817,7 +781,6 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
                        const uint8_t* attach_manifest = nullptr, size_t attach_manifest_bytes = 0) {
   e->cfg = *cfg;
   e->B = batch_size;
-  e->device = device_id;
   const dsm_asr_config& c = e->cfg;
   if (batch_size <= 0) { e->set_error("batch_size must be positive"); return DSM_ERR_INVALID; }
   if (c.audio_codebooks > 64 || c.audio_codebooks != c.mimi.quantizer_n_q) {
@@ -831,35 +794,14 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
   }
   if (c.extra_heads_num > DSM_MAX_EXTRA_HEADS) { e->set_error("too many extra heads"); return DSM_ERR_INVALID; }
   if (c.dot_mode != 0 && c.dot_mode != 1) { e->set_error("dot_mode must be 0 (f32 MFMA chain) or 1 (bx3)"); return DSM_ERR_INVALID; }
-  e->dot_mode = c.dot_mode;
-  for (const dsm_transformer_config* t : {&c.lm, &c.mimi.transformer}) {
-    if (t->d_model % t->num_heads || t->d_model % 32 || t->d_model > 4096) {
-      e->set_error("d_model must be a multiple of num_heads and of 32, and <= 4096 (the row-norm kernels keep a row in registers)");
-      return DSM_ERR_INVALID;
-    }
-    int hd = t->d_model / t->num_heads;
-    if (hd != 32 && hd != 64 && hd != 128) { e->set_error("head_dim %d unsupported (32, 64, 128)", hd); return DSM_ERR_INVALID; }
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_id) {
-    e->set_error("no usable HIP device %d (found %d): libdsm_mi355x has no CPU fallback", device_id, ndev);
-    return DSM_ERR_DEVICE;
-  }
-  HIPCHK(hipSetDevice(device_id));
-  dsm_read_env(e, true);
-  // Stream priorities (DSM_STREAM_PRIO=1: LM streams high, encoder stream low) are off by default: measured +0.5 % at
-  // B = 64 but -2.6 % at B = 400, where the encoder's share of the step is large and starving it delays the next frame.
-  int prio_lo = 0, prio_hi = 0;
-  if (e->stream_prio) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  e->prio_hi = prio_hi;
-  HIPCHK(hipStreamCreateWithPriority(&e->s_enc, hipStreamNonBlocking, prio_lo));
-  HIPCHK(hipStreamCreateWithPriority(&e->s_model, hipStreamNonBlocking, prio_hi));
-  HIPCHK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&e->ev_codes_consumed, hipEventDisableTiming));
-  HIPCHK(hipEventCreate(&e->ev_a));
-  HIPCHK(hipEventCreate(&e->ev_b));
-  HIPCHK(hipEventCreate(&e->ev_c));
-  HIPCHK(hipEventCreate(&e->ev_d));
+  for (const dsm_transformer_config* t : {&c.lm, &c.mimi.transformer})
+    if (int rc = check_transformer_config(e, *t)) return rc;
+  if (int rc = e->open(device_id, c.dot_mode, true)) return rc;
+  for (hipEvent_t* ev : {&e->ev_join, &e->ev_codes_consumed})
+    if (int rc = e->new_event(ev)) return rc;
+  for (hipEvent_t* ev : {&e->ev_a, &e->ev_b, &e->ev_c, &e->ev_d})
+    if (int rc = e->new_event(ev, hipEventDefault)) return rc;
+  for (auto& gs : e->g_enc) gs = e->graph_slot();
   const int B = batch_size, d = c.lm.d_model;
   // ---- weights: Mimi (f32, core/mimi.rs:261-276) + LM (bf16, srv/batched_asr.rs:738-745) into one arena ----
   if (attach_arena) {
@@ -913,11 +855,7 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
   if (int rc = alloc_mimi_state(e, &e->mimi[0], e->mimi_w, B)) return rc;  // mimi[1]: ensure_model_side_mimi, on first use
   LmState& s = e->lm;
   const int hid = c.lm.gating ? gating_hidden(c.lm) : c.lm.dim_feedforward;
-  if (int rc = e->dalloc(&s.x, (size_t)B * d)) return rc;
-  if (int rc = e->dalloc(&s.xn, (size_t)B * d)) return rc;
-  if (int rc = e->dalloc(&s.q, (size_t)B * d)) return rc;
-  if (int rc = e->dalloc(&s.att, (size_t)B * d)) return rc;
-  if (int rc = e->dalloc(&s.g, (size_t)B * hid)) return rc;
+  if (int rc = alloc_act(e, &s.act, B, d, hid)) return rc;
   if (int rc = e->dalloc(&s.hidden, (size_t)B * d)) return rc;
   if (int rc = e->dalloc(&s.logits, (size_t)B * c.text_out_vocab_size)) return rc;
   if (int rc = e->dalloc(&s.eh, (size_t)B * (c.extra_heads_num * c.extra_heads_dim + 1))) return rc;
@@ -947,8 +885,6 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
     const int n16 = (B + 15) / 16;
     if (G > n16) G = n16;
     s.groups.resize(G);
-    const int H = c.lm.num_heads, hd = d / H;
-    const size_t kv_elem = c.kv_bf16 ? 2 : 4;
     int b0 = 0;
     for (int g = 0; g < G; ++g) {
       int blocks = n16 / G + (g < n16 % G ? 1 : 0);
@@ -956,25 +892,15 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
       LmState::Group& grp = s.groups[g];
       grp.b0 = b0;
       grp.nb = nb;
-      grp.view = s.tr;
-      for (int l = 0; l < c.lm.num_layers; ++l) {
-        grp.view.k[l] = (char*)s.tr.k[l] + (size_t)b0 * H * c.lm.context * hd * kv_elem;
-        grp.view.v[l] = (char*)s.tr.v[l] + (size_t)b0 * H * c.lm.context * hd * kv_elem;
-      }
-      grp.view.pos = s.tr.pos + b0;
-      grp.view.idx = s.tr.idx + b0;
-      grp.view.start_pos = s.tr.start_pos + b0;
-      grp.view.widx = s.tr.widx + b0;             // T = 1
-      grp.view.rope_cs = s.tr.rope_cs + (size_t)b0 * hd;
+      grp.view = group_view(s.tr, c.lm, c.kv_bf16 ? 2 : 4, b0);
       b0 += nb;
-      if (g > 0) {
-        HIPCHK(hipStreamCreateWithPriority(&e->s_grp[g], hipStreamNonBlocking, e->prio_hi));
-        HIPCHK(hipEventCreateWithFlags(&e->ev_grp_in[g], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&e->ev_grp_done[g], hipEventDisableTiming));
-      }
+      e->g_grp[g] = e->graph_slot();
+      if (g > 0)
+        if (int rc = e->new_event(&e->ev_grp_in[g])) return rc;
     }
-    HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    for (int g = 0; g + 1 < G; ++g) HIPCHK(hipEventCreateWithFlags(&e->ev_stagger[g], hipEventDisableTiming));
+    if (int rc = e->open_groups(G)) return rc;
+    for (int g = 0; g + 1 < G; ++g)
+      if (int rc = e->new_event(&e->ev_stagger[g])) return rc;
   }
   // State::new — core/asr.rs:65-88: next_codebooks = audio_pad_token, text_token = text_start_token, step_idx = 0
   {
@@ -987,12 +913,12 @@ static int create_impl(dsm_engine* e, const dsm_asr_config* cfg, int device_id, 
     HIPCHK(hipMemsetAsync(s.first_step, 1, B, e->s_model));
   }
   e->items.assign(B, HostItem());
-  HIPCHK(hipHostMalloc((void**)&e->h_pcm, sizeof(float) * (size_t)B * DSM_FRAME_SIZE));
-  HIPCHK(hipHostMalloc((void**)&e->h_pcm1, sizeof(float) * (size_t)B * DSM_FRAME_SIZE));
-  HIPCHK(hipHostMalloc((void**)&e->h_mask, (size_t)B));
-  HIPCHK(hipHostMalloc((void**)&e->h_codes, sizeof(uint32_t) * (size_t)B * c.audio_codebooks));
-  HIPCHK(hipHostMalloc((void**)&e->h_text, sizeof(uint32_t) * (size_t)B));
-  HIPCHK(hipHostMalloc((void**)&e->h_prs, sizeof(float) * (size_t)B * (c.extra_heads_num + 1)));
+  if (int rc = e->halloc(&e->h_pcm, (size_t)B * DSM_FRAME_SIZE)) return rc;
+  if (int rc = e->halloc(&e->h_pcm1, (size_t)B * DSM_FRAME_SIZE)) return rc;
+  if (int rc = e->halloc(&e->h_mask, (size_t)B)) return rc;
+  if (int rc = e->halloc(&e->h_codes, (size_t)B * c.audio_codebooks)) return rc;
+  if (int rc = e->halloc(&e->h_text, (size_t)B)) return rc;
+  if (int rc = e->halloc(&e->h_prs, (size_t)B * (c.extra_heads_num + 1))) return rc;
   HIPCHK(hipDeviceSynchronize());
   e->metrics.algorithmic_bytes_lm = lm_algorithmic_bytes(e);
   e->metrics.algorithmic_bytes_encode = mimi_enc_algorithmic_bytes(e);
@@ -1006,15 +932,7 @@ int dsm_asr_create(const dsm_asr_config* cfg, int device_id, int batch_size, con
     return DSM_ERR_INVALID;
   }
   dsm_engine* e = new dsm_engine();
-  int rc = create_impl(e, cfg, device_id, batch_size, lm_safetensors, mimi_safetensors);
-  if (rc) {
-    g_create_error = e->err;
-    dsm_destroy(e);
-    *out = nullptr;
-    return rc;
-  }
-  *out = e;
-  return 0;
+  return finish_create(e, create_impl(e, cfg, device_id, batch_size, lm_safetensors, mimi_safetensors), out);
 }
 
 int dsm_asr_weight_arena(dsm_engine* e, void** d_arena, size_t* arena_bytes, const uint8_t** manifest, size_t* manifest_bytes) {
@@ -1033,15 +951,7 @@ int dsm_asr_create_from_arena(const dsm_asr_config* cfg, int device_id, int batc
     return DSM_ERR_INVALID;
   }
   dsm_engine* e = new dsm_engine();
-  int rc = create_impl(e, cfg, device_id, batch_size, nullptr, nullptr, d_arena, arena_bytes, manifest, manifest_bytes);
-  if (rc) {
-    g_create_error = e->err;
-    dsm_destroy(e);
-    *out = nullptr;
-    return rc;
-  }
-  *out = e;
-  return 0;
+  return finish_create(e, create_impl(e, cfg, device_id, batch_size, nullptr, nullptr, d_arena, arena_bytes, manifest, manifest_bytes), out);
 }
 
 // One process, several devices (r04; the reference is one process, srv/main.rs:317-327, and a Rust host has no torch.distributed):
@@ -1232,11 +1142,11 @@ static int pipe_init(dsm_engine* e) {
   if (e->pipe_ready) return 0;
   const size_t B = (size_t)e->B, nq = (size_t)e->cfg.mimi.quantizer_n_q;
   for (auto& ps : e->pipe) {
-    HIPCHK(hipHostMalloc((void**)&ps.h_pcm, sizeof(float) * B * DSM_FRAME_SIZE));
-    HIPCHK(hipHostMalloc((void**)&ps.h_mask, B));
+    if (int rc = e->halloc(&ps.h_pcm, B * DSM_FRAME_SIZE)) return rc;
+    if (int rc = e->halloc(&ps.h_mask, B)) return rc;
     if (int rc = e->dalloc(&ps.d_codes, B * nq)) return rc;
-    HIPCHK(hipEventCreateWithFlags(&ps.ev_done, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ps.ev_consumed, hipEventDisableTiming));
+    if (int rc = e->new_event(&ps.ev_done)) return rc;
+    if (int rc = e->new_event(&ps.ev_consumed)) return rc;
   }
   e->pipe_ready = true;
   return 0;
@@ -1319,17 +1229,16 @@ int dsm_mimi_decode_step(dsm_engine* e, const uint32_t* codes, const uint8_t* ma
   if (!e || !codes || !mask) return DSM_ERR_INVALID;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
-  if (!e->dec.ready)
-    if (int rc = alloc_dec_state(e)) return rc;
+  if (int rc = alloc_dec_state(e, e->mimi_w, e->dec, e->B)) return rc;
   MimiDecState& s = e->dec;
   hipStream_t st = e->s_enc;
   std::vector<uint8_t> m(mask, mask + e->B);
   HIPCHK(hipMemcpyAsync(s.codes, codes, sizeof(uint32_t) * (size_t)e->B * e->cfg.mimi.quantizer_n_q, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(s.mask, m.data(), (size_t)e->B, hipMemcpyHostToDevice, st));
-  if (int rc = mimi_decode(e, st)) return rc;
-  HIPCHK(hipMemcpyAsync(e->h_pcm_out, s.pcm, sizeof(float) * (size_t)e->B * DSM_FRAME_SIZE, hipMemcpyDeviceToHost, st));
+  if (int rc = mimi_decode(e, e->mimi_w, s, e->B, st)) return rc;
+  HIPCHK(hipMemcpyAsync(s.h_pcm_out, s.pcm, sizeof(float) * (size_t)e->B * DSM_FRAME_SIZE, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (pcm_out) memcpy(pcm_out, e->h_pcm_out, sizeof(float) * (size_t)e->B * DSM_FRAME_SIZE);
+  if (pcm_out) memcpy(pcm_out, s.h_pcm_out, sizeof(float) * (size_t)e->B * DSM_FRAME_SIZE);
   if (produced) *produced = DSM_FRAME_SIZE;
   return 0;
 }
@@ -1338,13 +1247,12 @@ int dsm_mimi_decode_step_dev(dsm_engine* e, const uint32_t* d_codes, const uint8
   if (!e || !d_codes || !d_mask) return DSM_ERR_INVALID;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
-  if (!e->dec.ready)
-    if (int rc = alloc_dec_state(e)) return rc;
+  if (int rc = alloc_dec_state(e, e->mimi_w, e->dec, e->B)) return rc;
   MimiDecState& s = e->dec;
   hipStream_t st = e->s_enc;
   HIPCHK(hipMemcpyAsync(s.codes, d_codes, sizeof(uint32_t) * (size_t)e->B * e->cfg.mimi.quantizer_n_q, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(s.mask, d_mask, (size_t)e->B, hipMemcpyDeviceToDevice, st));
-  if (int rc = mimi_decode(e, st)) return rc;
+  if (int rc = mimi_decode(e, e->mimi_w, s, e->B, st)) return rc;
   if (d_pcm_out)
     HIPCHK(hipMemcpyAsync(d_pcm_out, s.pcm, sizeof(float) * (size_t)e->B * DSM_FRAME_SIZE, hipMemcpyDeviceToDevice, st));
   return 0;
@@ -1404,18 +1312,10 @@ int dsm_mimi_reset_slot(dsm_engine* e, int slot) {
   return reset_mimi_slot(e, 0, e->s_enc, slot);
 }
 
-static void fill_graph_metrics(dsm_engine* e, dsm_metrics* out) {
-  out->graph_launches = e->graph_launches;
-  out->eager_bodies = e->eager_bodies;
-  out->capture_failures = e->capture_failures;
-  std::lock_guard<std::mutex> lk(e->err_mu);
-  snprintf(out->capture_error, sizeof out->capture_error, "%s", e->capture_error.c_str());
-}
-
 int dsm_get_metrics(dsm_engine* e, dsm_metrics* out) {
   if (!e || !out) return DSM_ERR_INVALID;
   *out = e->metrics;
-  fill_graph_metrics(e, out);
+  e->fill_graph_metrics(out);
   return 0;
 }
 
@@ -1491,10 +1391,7 @@ int dsm_prof_enable(dsm_engine* e, unsigned tag_mask) {
   if (tag_mask && !e->dev_ts) {  // launch-bracket records for dsm_prof_read_device: (min start, max end) per launch
     HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, sizeof(unsigned long long) * 2 * dsm_engine::kDevTsCap));
-    e->allocs.push_back(p);
-    e->dev_ts = reinterpret_cast<unsigned long long*>(p);
+    if (int rc = e->dalloc(&e->dev_ts, 2 * dsm_engine::kDevTsCap, false)) return rc;
     std::vector<unsigned long long> init(2 * dsm_engine::kDevTsCap);
     for (size_t i = 0; i < dsm_engine::kDevTsCap; ++i) { init[2 * i] = ~0ull; init[2 * i + 1] = 0; }
     HIPCHK(hipMemcpy(e->dev_ts, init.data(), sizeof(unsigned long long) * init.size(), hipMemcpyHostToDevice));

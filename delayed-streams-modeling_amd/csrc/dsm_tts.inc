@@ -1,11 +1,13 @@
-// dsm_tts.inc — TTS step (BASELINE.json configs[4]): tts_streaming::State::step over B independent generations
-// (included by dsm_engine.hip).  Device work: input embedding sum, main LM (RoPE at the pre-append position, like the
+// dsm_tts.inc — TTS step (BASELINE.json configs[4]): tts_streaming::State::step over B independent generations (part of the
+// library's one translation unit).  Device work: input embedding sum, main LM (RoPE at the pre-append position, like the
 // non-batched transformer the TTS worker builds: srv/tts.rs:345), text-token rule, then the DepFormer — num_slices
 // sequential passes of one shared transformer whose KV sequence is the slice axis (core/lm.rs:640-684).  The per-slot
 // delayed-streams bookkeeping (core/tts_streaming.rs:117-242) is integer work on the host, one upload and one
-// download per step.  With a Mimi attached (dsm_tts_attach_mimi) dsm_tts_step_pcm also decodes the frame each step completes,
-// on the engine's second stream (the audio_processing_loop of srv/tts.rs:528-544): the frame is assembled on the device
-// (tts_frame_kernel) and the decode of step n overlaps the LM of step n + 1.
+// download per step.  The engine is a DsmDevice (dsm_device.h) plus the TTS model: it shares the context type, the loaders,
+// transformer_forward and the Mimi decoder with the STT engine, and none of that engine's state.  With a Mimi attached
+// (dsm_tts_attach_mimi) dsm_tts_step_pcm also decodes the frame each step completes, on the context's second stream (the
+// audio_processing_loop of srv/tts.rs:528-544): the frame is assembled on the device (tts_frame_kernel) and the decode of
+// step n overlaps the LM of step n + 1.
 
 namespace {
 
@@ -18,18 +20,17 @@ struct DepW {
 
 }  // namespace
 
-struct dsm_tts {
+struct dsm_tts : DsmDevice {
   dsm_tts_config cfg{};
   int B = 0;
   // batch rows: a slot owns rps consecutive rows of every activation and cache (2 with cfg_rows: the conditional and the
   // unconditional row of classifier-free guidance, core/tts_streaming.rs:122); R = B * rps
   int rps = 1, R = 0;
-  dsm_engine* eng = nullptr;  // streams, allocations, GEMM workspaces, error text
   LmW lm;
   DepW dep;
   // device state
-  float *x = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *g = nullptr, *hidden = nullptr, *logits = nullptr;
-  float *dx = nullptr, *dxn = nullptr, *dq = nullptr, *datt = nullptr, *dg = nullptr, *dproj = nullptr, *dlogits = nullptr;
+  ActScratch act, dact;  // main LM, depformer
+  float *hidden = nullptr, *logits = nullptr, *dproj = nullptr, *dlogits = nullptr;
   int32_t *d_tokens = nullptr, *d_allowed = nullptr;
   uint8_t *d_mask = nullptr, *d_force_eop = nullptr, *d_run = nullptr, *d_forced = nullptr;  // per slot
   uint8_t *d_rmask = nullptr, *d_rrun = nullptr, *d_ca_act = nullptr;                        // per batch row
@@ -58,6 +59,7 @@ struct dsm_tts {
     CaState ca;
   };
   std::vector<Grp> groups;
+  GraphSlot* g_ttsg[kMaxGroups][2] = {};  // per group: the step without / with the depformer
   // pinned staging
   int32_t *h_tokens = nullptr, *h_allowed = nullptr;
   uint8_t* h_flags = nullptr;  // [4][B]: mask, force_eop, run, forced; [3][R] row flags; then (4-byte aligned) step_idx [B] i32, frame buffer u8
@@ -78,7 +80,9 @@ struct dsm_tts {
   uint8_t* d_fsel = nullptr;
   uint32_t *d_ring = nullptr, *d_row0 = nullptr, *d_fcodes = nullptr;  // [B][ad + 1], [B][S], [3][B][S]
   uint8_t* d_fvalid = nullptr;                                          // [3][B]
-  bool mimi = false;
+  bool mimi = false;  // mimi_w and dec are loaded: dsm_tts_step_pcm is available
+  MimiW mimi_w;
+  MimiDecState dec;
   hipEvent_t ev_frames = nullptr;
   struct PcmEntry {  // one deferred step: its PCM / valid land in pinned memory behind `ev`
     hipEvent_t ev = nullptr;
@@ -94,11 +98,9 @@ struct dsm_tts {
 namespace {
 
 int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int batch_size, const char* lm_path) {
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   t->cfg = *cfg;
   t->B = batch_size;
-  e->B = batch_size;
-  e->device = device_id;
   const dsm_tts_config& c = t->cfg;
   const int B = batch_size, d = c.lm.d_model, D = c.depformer.d_model, S = c.dep_num_slices, G = c.dep_weight_groups;
   if (B <= 0) { e->set_error("batch_size must be positive"); return DSM_ERR_INVALID; }
@@ -111,11 +113,8 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
     e->set_error("TTS path expects gated RMS-norm transformers and a depformer without positional embedding");
     return DSM_ERR_INVALID;
   }
-  for (const dsm_transformer_config* tc : {&c.lm, &c.depformer}) {
-    if (tc->d_model % tc->num_heads || tc->d_model % 32 || tc->d_model > 4096) { e->set_error("unsupported d_model"); return DSM_ERR_INVALID; }
-    int hd = tc->d_model / tc->num_heads;
-    if (hd != 32 && hd != 64 && hd != 128) { e->set_error("head_dim %d unsupported (32, 64, 128)", hd); return DSM_ERR_INVALID; }
-  }
+  for (const dsm_transformer_config* tc : {&c.lm, &c.depformer})
+    if (int rc = check_transformer_config(e, *tc)) return rc;
   if (c.acoustic_delay < 0 || c.text_audio_delay_in_tokens < 0) { e->set_error("negative delay"); return DSM_ERR_INVALID; }
   if (c.dep_low_rank % 4) { e->set_error("low_rank_embeddings must be a multiple of 4"); return DSM_ERR_INVALID; }
   if (c.cross_attention && (c.ca_max_len <= 0 || c.ca_dim < 0 || (c.ca_dim % 4) != 0)) {
@@ -128,16 +127,7 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
   t->rps = c.cfg_rows ? 2 : 1;
   t->R = B * t->rps;
   if (c.dot_mode != 0 && c.dot_mode != 1) { e->set_error("dot_mode must be 0 or 1"); return DSM_ERR_INVALID; }
-  e->dot_mode = c.dot_mode;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_id) {
-    e->set_error("no usable HIP device %d (found %d): libdsm_mi355x has no CPU fallback", device_id, ndev);
-    return DSM_ERR_DEVICE;
-  }
-  HIPCHK(hipSetDevice(device_id));
-  dsm_read_env(e, false);
-  HIPCHK(hipStreamCreateWithFlags(&e->s_enc, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&e->s_model, hipStreamNonBlocking));
+  if (int rc = e->open(device_id, c.dot_mode, false)) return rc;
   hipStream_t st = e->s_model;
   char err[512];
   dsm_st_file* f = dsm_st_open(lm_path, err, sizeof err);
@@ -145,19 +135,7 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
   Loader ld{e, f};
   int rc = 0;
   do {
-    auto te = ld.get((int64_t)c.text_in_vocab_size * d, "text_emb.weight");
-    if (ld.failed) { rc = DSM_ERR_IO; break; }
-    std::vector<uint16_t> tb(te.size());
-    for (size_t i = 0; i < te.size(); ++i) tb[i] = dsm_f32_to_bf16(te[i]);
-    if ((rc = e->upload(&t->lm.text_emb, tb.data(), tb.size()))) break;
-    std::vector<uint16_t> ab((size_t)c.audio_codebooks * c.audio_vocab_size * d);
-    for (int i = 0; i < c.audio_codebooks && !ld.failed; ++i) {
-      auto ae = ld.get((int64_t)c.audio_vocab_size * d, "emb.%d.weight", i);
-      for (size_t j = 0; j < ae.size(); ++j) ab[(size_t)i * c.audio_vocab_size * d + j] = dsm_f32_to_bf16(ae[j]);
-    }
-    if (ld.failed) { rc = DSM_ERR_IO; break; }
-    if ((rc = e->upload(&t->lm.audio_emb, ab.data(), ab.size()))) break;
-    if ((rc = load_transformer(e, ld, &t->lm.tr, c.lm, "transformer", true))) break;
+    if ((rc = load_lm_trunk(e, ld, &t->lm, c))) break;
     t->lm.tr.rope_pos_before = true;
     // a checkpoint with cross-attention tensors must not be run without them (ADVICE r03: the layers would be skipped silently)
     if (!c.cross_attention && (ld.has("transformer.layers.0.cross_attention.out_proj.weight") || ld.has("transformer.layers.0.norm_cross.weight") ||
@@ -200,11 +178,6 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
       }
       if (rc) break;
     }
-    auto on = ld.get(d, "out_norm.alpha");
-    auto tl = ld.get((int64_t)c.text_out_vocab_size * d, "text_linear.weight");
-    if (ld.failed) { rc = DSM_ERR_IO; break; }
-    if ((rc = e->upload(&t->lm.out_norm, on.data(), on.size()))) break;
-    if ((rc = pack_linear(e, &t->lm.text_linear, tl.data(), c.text_out_vocab_size, d, true, nullptr))) break;
     // ---- DepFormer ----
     DepW& w = t->dep;
     {  // the G input projections stacked row-wise (r03): depformer_in of every slice is a function of the main LM's output alone
@@ -278,18 +251,10 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
   if (rc) return rc;
   const int hid = gating_hidden(c.lm), dhid = gating_hidden(c.depformer), V = c.audio_vocab_size - 1;
   const int R = t->R, rps = t->rps;
-  if ((rc = e->dalloc(&t->x, (size_t)R * d))) return rc;
-  if ((rc = e->dalloc(&t->xn, (size_t)R * d))) return rc;
-  if ((rc = e->dalloc(&t->q, (size_t)R * d))) return rc;
-  if ((rc = e->dalloc(&t->att, (size_t)R * d))) return rc;
-  if ((rc = e->dalloc(&t->g, (size_t)R * hid))) return rc;
+  if ((rc = alloc_act(e, &t->act, R, d, hid))) return rc;
   if ((rc = e->dalloc(&t->hidden, (size_t)R * d))) return rc;
   if ((rc = e->dalloc(&t->logits, (size_t)R * c.text_out_vocab_size))) return rc;
-  if ((rc = e->dalloc(&t->dx, (size_t)R * D))) return rc;
-  if ((rc = e->dalloc(&t->dxn, (size_t)R * D))) return rc;
-  if ((rc = e->dalloc(&t->dq, (size_t)R * D))) return rc;
-  if ((rc = e->dalloc(&t->datt, (size_t)R * D))) return rc;
-  if ((rc = e->dalloc(&t->dg, (size_t)R * dhid))) return rc;
+  if ((rc = alloc_act(e, &t->dact, R, D, dhid))) return rc;
   if ((rc = e->dalloc(&t->dproj, (size_t)R * c.dep_weight_groups * D))) return rc;
   if ((rc = e->dalloc(&t->dlogits, (size_t)R * V))) return rc;
   if ((rc = e->dalloc(&t->d_tokens, (size_t)R * (1 + c.audio_codebooks)))) return rc;
@@ -357,53 +322,29 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
     int Gn = B >= 96 ? 2 : 1;  // measured (v202501, dot_mode 1): B = 32 8.4 vs 9.3 ms, 64 9.4 vs 10.1, 128 12.4 vs 11.7 (one vs two groups)
     Gn = dsm_env_int("DSM_TTS_GROUPS", Gn);
     if (Gn < 1) Gn = 1;
-    if (Gn > dsm_engine::kMaxGroups) Gn = dsm_engine::kMaxGroups;
+    if (Gn > DsmDevice::kMaxGroups) Gn = DsmDevice::kMaxGroups;
     if (Gn > B) Gn = B;
     t->groups.resize(Gn);
-    auto view = [&](const TransformerState& full, const dsm_transformer_config& tc, bool bf16, int r0) {
-      TransformerState v = full;
-      const int H = tc.num_heads, hd = tc.d_model / H;
-      const size_t elem = bf16 ? 2 : 4;
-      for (int l = 0; l < tc.num_layers; ++l) {
-        v.k[l] = (char*)full.k[l] + (size_t)r0 * H * tc.context * hd * elem;
-        v.v[l] = (char*)full.v[l] + (size_t)r0 * H * tc.context * hd * elem;
-      }
-      v.pos = full.pos + r0; v.idx = full.idx + r0; v.start_pos = full.start_pos + r0; v.widx = full.widx + r0;  // T = 1
-      v.rope_cs = full.rope_cs + (size_t)r0 * hd;
-      return v;
-    };
     int b0 = 0;
     for (int g = 0; g < Gn; ++g) {
       const int nb = B / Gn + (g < B % Gn ? 1 : 0);
       dsm_tts::Grp& grp = t->groups[g];
       grp.b0 = b0; grp.nb = nb;
       const int r0 = b0 * rps;
-      grp.tr = view(t->tr, c.lm, c.kv_bf16 != 0, r0);
-      grp.dtr = view(t->dtr, c.depformer, false, r0);
-      if (c.cross_attention) {
-        grp.ca = t->ca;
-        for (int l = 0; l < c.lm.num_layers; ++l) {
-          grp.ca.k[l] = (char*)t->ca.k[l] + (size_t)r0 * d * t->ca.smax * kv_elem;
-          grp.ca.v[l] = (char*)t->ca.v[l] + (size_t)r0 * d * t->ca.smax * kv_elem;
-        }
-        grp.ca.last = t->ca.last + r0;
-        grp.ca.act = t->ca.act + r0;
-        grp.ca.att = t->ca.att + (size_t)r0 * d;
-      }
+      grp.tr = group_view(t->tr, c.lm, kv_elem, r0);
+      grp.dtr = group_view(t->dtr, c.depformer, 4, r0);
+      if (c.cross_attention) grp.ca = group_view(t->ca, d, kv_elem, r0);
       b0 += nb;
-      if (g > 0) {
-        HIPCHK(hipStreamCreateWithFlags(&e->s_grp[g], hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&e->ev_grp_done[g], hipEventDisableTiming));
-      }
+      for (auto& gs : t->g_ttsg[g]) gs = e->graph_slot();
     }
-    HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+    if ((rc = e->open_groups(Gn))) return rc;
   }
-  HIPCHK(hipHostMalloc((void**)&t->h_tokens, sizeof(int32_t) * (size_t)R * (1 + c.audio_codebooks)));
-  HIPCHK(hipHostMalloc((void**)&t->h_allowed, sizeof(int32_t) * (size_t)B));
-  HIPCHK(hipHostMalloc((void**)&t->h_flags, t->flags_bytes));
+  if ((rc = e->halloc(&t->h_tokens, (size_t)R * (1 + c.audio_codebooks)))) return rc;
+  if ((rc = e->halloc(&t->h_allowed, (size_t)B))) return rc;
+  if ((rc = e->halloc(&t->h_flags, t->flags_bytes))) return rc;
   memset(t->h_flags, 0, t->flags_bytes);
-  HIPCHK(hipHostMalloc((void**)&t->h_text_token, sizeof(uint32_t) * (size_t)B));
-  HIPCHK(hipHostMalloc((void**)&t->h_lat, sizeof(uint32_t) * (size_t)B * S));
+  if ((rc = e->halloc(&t->h_text_token, (size_t)B))) return rc;
+  if ((rc = e->halloc(&t->h_lat, (size_t)B * S))) return rc;
   t->n_steps = (size_t)c.max_steps + c.acoustic_delay;
   t->items.resize(B);
   for (auto& it : t->items) {
@@ -439,13 +380,13 @@ SampleArgs sample_args(const dsm_tts* t, int V, uint32_t* pos, int b0) {  // the
 // DepFormer::sample — core/lm.rs:640-684 for the slots of one stream group, all slices enqueued back to back, tokens stay on
 // the device
 int tts_depformer(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp) {
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   const dsm_tts_config& c = t->cfg;
   const int d = c.lm.d_model, D = c.depformer.d_model, S = c.dep_num_slices, G = c.dep_weight_groups;
   const int V = c.audio_vocab_size - 1, dhid = gating_hidden(c.depformer);
   const int rps = t->rps, b0 = grp.b0, nslots = grp.nb, r0 = b0 * rps, B = nslots * rps;  // B: batch rows of this group from here on
-  float *dx = t->dx + (size_t)r0 * D, *dxn = t->dxn + (size_t)r0 * D, *dq = t->dq + (size_t)r0 * D,
-        *datt = t->datt + (size_t)r0 * D, *dg = t->dg + (size_t)r0 * dhid, *dlogits = t->dlogits + (size_t)r0 * V;
+  const ActScratch da = t->dact.from_row(r0, D, dhid);
+  float* dlogits = t->dlogits + (size_t)r0 * V;
   const float* hidden = t->hidden + (size_t)r0 * d;
   // depformer_in.{g}(hidden) for every weight group in one GEMM (r03): the projection of slice k does not depend on the
   // tokens sampled before it, only its embedding does — 32 x (GEMM + reduce) per step become one pair
@@ -465,7 +406,7 @@ int tts_depformer(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp) {
     const int g = (k * G) / S;
     const TransformerW& tw = t->dep.tr[g];
     DepHeadArgs h;
-    h.x = dx; h.xn = dxn; h.table = t->dep.emb[k];
+    h.x = da.x; h.xn = da.xn; h.table = t->dep.emb[k];
     h.vocab = k == 0 ? c.text_in_vocab_size : c.audio_vocab_size;
     h.D = D; h.rps = rps;
     h.proj = dproj + (size_t)g * D; h.proj_ld = (long)G * D;
@@ -482,12 +423,12 @@ int tts_depformer(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp) {
       hipLaunchKernelGGL(dep_head_kernel, dim3(B), dim3(256), 0, st, head_args(0), t->d_last + b0);
       HIPCHK(hipGetLastError());
     }
-    if (int rc = transformer_forward<uint16_t, float>(e, st, tw, grp.dtr, dx, dxn, dq, datt, dg, B, 1, t->d_rrun + r0,
+    if (int rc = transformer_forward<uint16_t, float>(e, st, tw, grp.dtr, da.x, da.xn, da.q, da.att, da.g, B, 1, t->d_rrun + r0,
                                                       nullptr, plain_map(1, 1), nullptr, nullptr, 0, nullptr, /*head_done=*/true))
       return rc;
     LogitSrc src{};
     {
-      GemmArgs a = base_args(t->dep.out[k], dx, plain_map(B, D), B);
+      GemmArgs a = base_args(t->dep.out[k], da.x, plain_map(B, D), B);
       a.Y = dlogits; a.ymap = plain_map(B, V);
       // a split-K product with a plain epilogue: leave the slabs to the sampler launch (one launch less per slice)
       a.defer_reduce = (a.Kpad > DSM_KC && a.K % 32 == 0 && !a.bias && V % 4 == 0) ? 1 : 0;
@@ -518,25 +459,22 @@ int tts_depformer(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp) {
 
 // The device side of State::step for one stream group: input embedding sum, main LM, text-token rule, depformer.
 int tts_group_body(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp, bool run_dep) {
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   const dsm_tts_config& c = t->cfg;
   const int d = c.lm.d_model, nc = c.audio_codebooks, hid = gating_hidden(c.lm), Vt = c.text_out_vocab_size;
   const int rps = t->rps, b0 = grp.b0, nslots = grp.nb, r0 = b0 * rps, B = nslots * rps, sid = e->sid(st);  // B: batch rows of the group
-  float *x = t->x + (size_t)r0 * d, *xn = t->xn + (size_t)r0 * d, *q = t->q + (size_t)r0 * d, *att = t->att + (size_t)r0 * d,
-        *gg = t->g + (size_t)r0 * hid, *hidden = t->hidden + (size_t)r0 * d, *logits = t->logits + (size_t)r0 * Vt;
+  const ActScratch sc = t->act.from_row(r0, d, hid);
+  float *hidden = t->hidden + (size_t)r0 * d, *logits = t->logits + (size_t)r0 * Vt;
   const CaState* ca = c.cross_attention ? &grp.ca : nullptr;
   e->tag_gemm[sid] = DSM_PROF_GEMM_LM;
   e->tag_attn[sid] = DSM_PROF_ATTN_LM;
-  hipLaunchKernelGGL(tts_input_kernel, dim3(B, (d + 511) / 512), dim3(256), 0, st, x, t->lm.text_emb, t->lm.audio_emb,
+  hipLaunchKernelGGL(tts_input_kernel, dim3(B, (d + 511) / 512), dim3(256), 0, st, sc.x, t->lm.text_emb, t->lm.audio_emb,
                      t->d_tokens + (size_t)r0 * (1 + nc), nc, d, c.audio_vocab_size);
   HIPCHK(hipGetLastError());
-  int rc;  // forward_cond, or forward_ca for rows that carry a source (core/lm.rs:957-1067)
-  if (c.kv_bf16)
-    rc = transformer_forward<uint16_t, uint16_t>(e, st, t->lm.tr, grp.tr, x, xn, q, att, gg, B, 1, t->d_rmask + r0, nullptr,
-                                                 plain_map(1, 1), t->lm.out_norm, hidden, 0, ca);
-  else
-    rc = transformer_forward<uint16_t, float>(e, st, t->lm.tr, grp.tr, x, xn, q, att, gg, B, 1, t->d_rmask + r0, nullptr,
-                                              plain_map(1, 1), t->lm.out_norm, hidden, 0, ca);
+  int rc = with_kv_type(c.kv_bf16 != 0, [&](auto kv) {  // forward_cond, or forward_ca for rows that carry a source (core/lm.rs:957-1067)
+    return transformer_forward<uint16_t, decltype(kv)>(e, st, t->lm.tr, grp.tr, sc.x, sc.xn, sc.q, sc.att, sc.g, B, 1, t->d_rmask + r0, nullptr,
+                                                       plain_map(1, 1), t->lm.out_norm, hidden, 0, ca);
+  });
   if (rc) return rc;
   {
     GemmArgs a = base_args(t->lm.text_linear, hidden, plain_map(B, d), B);
@@ -577,15 +515,15 @@ int tts_group_body(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp, bool run_dep) 
 // Mimi::decode_step of the frames buffer `sel` holds, on the decode stream behind the step's groups; PCM and valid flags go
 // to the entry's pinned buffers, its event closes the sequence.
 int tts_enqueue_decode(dsm_tts* t, int sel, dsm_tts::PcmEntry& en) {
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   const int B = t->B, S = t->cfg.dep_num_slices;
   hipStream_t sd = e->s_enc;
-  MimiDecState& d = e->dec;
+  MimiDecState& d = t->dec;
   HIPCHK(hipEventRecord(t->ev_frames, e->s_model));  // the model stream has joined every group
   HIPCHK(hipStreamWaitEvent(sd, t->ev_frames, 0));
   HIPCHK(hipMemcpyAsync(d.codes, t->d_fcodes + (size_t)sel * B * S, sizeof(uint32_t) * (size_t)B * S, hipMemcpyDeviceToDevice, sd));
   HIPCHK(hipMemcpyAsync(d.mask, t->d_fvalid + (size_t)sel * B, (size_t)B, hipMemcpyDeviceToDevice, sd));
-  if (int rc = mimi_decode(e, sd)) return rc;
+  if (int rc = mimi_decode(e, t->mimi_w, d, B, sd)) return rc;
   HIPCHK(hipMemcpyAsync(en.h_pcm, d.pcm, sizeof(float) * (size_t)B * DSM_FRAME_SIZE, hipMemcpyDeviceToHost, sd));
   HIPCHK(hipMemcpyAsync(en.h_valid, d.mask, (size_t)B, hipMemcpyDeviceToHost, sd));
   HIPCHK(hipEventRecord(en.ev, sd));
@@ -595,7 +533,7 @@ int tts_enqueue_decode(dsm_tts* t, int sel, dsm_tts::PcmEntry& en) {
 
 // the oldest pending entry: wait for it, hand it out
 int tts_deliver_pcm(dsm_tts* t, float* pcm_out, uint8_t* pcm_valid_out) {
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   dsm_tts::PcmEntry& en = t->pcm_q[(t->pcm_seq - (uint64_t)t->pcm_pending) & 1];
   if (en.launched) HIPCHK(hipEventSynchronize(en.ev));
   for (int b = 0; b < t->B; ++b) {
@@ -613,22 +551,9 @@ extern "C" {
 
 void dsm_tts_config_v202501(dsm_tts_config* out) { dsm_preset_tts_v202501(out); }
 
-const char* dsm_tts_last_error(const dsm_tts* t) { return t ? t->eng->err.c_str() : g_create_error.c_str(); }
+const char* dsm_tts_last_error(const dsm_tts* t) { return t ? t->err.c_str() : g_create_error.c_str(); }
 
-void dsm_tts_destroy(dsm_tts* t) {
-  if (!t) return;
-  if (t->eng) {
-    (void)hipSetDevice(t->eng->device);
-    (void)hipDeviceSynchronize();
-  }
-  for (void* p : {(void*)t->h_tokens, (void*)t->h_allowed, (void*)t->h_flags, (void*)t->h_text_token, (void*)t->h_lat,
-                  (void*)t->pcm_q[0].h_pcm, (void*)t->pcm_q[1].h_pcm, (void*)t->pcm_q[0].h_valid, (void*)t->pcm_q[1].h_valid})
-    if (p) (void)hipHostFree(p);
-  for (hipEvent_t ev : {t->ev_frames, t->pcm_q[0].ev, t->pcm_q[1].ev})
-    if (ev) (void)hipEventDestroy(ev);
-  dsm_destroy(t->eng);
-  delete t;
-}
+void dsm_tts_destroy(dsm_tts* t) { delete t; }  // ~DsmDevice releases what the engine was handed
 
 int dsm_tts_create(const dsm_tts_config* cfg, int device_id, int batch_size, const char* lm_safetensors, dsm_tts** out) {
   if (!cfg || !out || !lm_safetensors) {
@@ -636,16 +561,7 @@ int dsm_tts_create(const dsm_tts_config* cfg, int device_id, int batch_size, con
     return DSM_ERR_INVALID;
   }
   dsm_tts* t = new dsm_tts();
-  t->eng = new dsm_engine();
-  int rc = tts_create_impl(t, cfg, device_id, batch_size, lm_safetensors);
-  if (rc) {
-    g_create_error = t->eng->err;
-    dsm_tts_destroy(t);
-    *out = nullptr;
-    return rc;
-  }
-  *out = t;
-  return 0;
+  return finish_create(t, tts_create_impl(t, cfg, device_id, batch_size, lm_safetensors), out);
 }
 
 }  // extern "C" (reopened below)
@@ -655,7 +571,7 @@ namespace {
 // checked that the entry is free); otherwise the frame goes to the spare buffer and is dropped.
 int tts_step_impl(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* allowed, const uint8_t* mask,
                   uint32_t* text_token_out, uint32_t* audio_out, bool decode) {
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   const dsm_tts_config& c = t->cfg;
   const int B = t->B, S = c.dep_num_slices, nc = c.audio_codebooks;
   const uint32_t pad = (uint32_t)c.audio_vocab_size - 1, UNG = DSM_TTS_UNGENERATED;
@@ -718,22 +634,17 @@ int tts_step_impl(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* al
   // group once its two variants (with / without the depformer) have each run twice: the step is launch-bound otherwise.
   // Groups fork from the model stream behind the uploads and join it again before the downloads.
   const size_t Gn = t->groups.size();
-  if (Gn > 1) {
-    HIPCHK(hipEventRecord(e->ev_fork, st));
-    for (size_t g = 1; g < Gn; ++g) HIPCHK(hipStreamWaitEvent(e->s_grp[g], e->ev_fork, 0));
-  }
-  for (size_t g = Gn; g-- > 0;) {  // the trailing groups first: the model stream is the one the downloads queue behind
-    dsm_tts::Grp& grp = t->groups[g];
-    hipStream_t gs = g == 0 ? st : e->s_grp[g];
-    bool run_dep = false;
-    for (int b = grp.b0; b < grp.b0 + grp.nb; ++b) run_dep = run_dep || h_run[b];
-    // graph variants: with / without the depformer; the key also tells sampling launches (LDS, argument) from ArgMax ones
-    if (int rc = run_captured(e, e->g_ttsg[g][run_dep ? 1 : 0], gs, (run_dep ? 1 : 0) | (tts_any_sampling(t) ? 2 : 0),
-                              [&] { return tts_group_body(t, gs, grp, run_dep); }))
-      return rc;
-    if (g > 0) HIPCHK(hipEventRecord(e->ev_grp_done[g], gs));
-  }
-  for (size_t g = 1; g < Gn; ++g) HIPCHK(hipStreamWaitEvent(st, e->ev_grp_done[g], 0));  // join: only after every group was launched
+  if (int rc = fork_groups(e, st, Gn)) return rc;
+  if (int rc = run_groups(e, st, Gn, false, [&](size_t g, hipStream_t gs) {
+        dsm_tts::Grp& grp = t->groups[g];
+        bool run_dep = false;
+        for (int b = grp.b0; b < grp.b0 + grp.nb; ++b) run_dep = run_dep || h_run[b];
+        // graph variants: with / without the depformer; the key also tells sampling launches (LDS, argument) from ArgMax ones
+        return run_captured(e, *t->g_ttsg[g][run_dep ? 1 : 0], gs, (run_dep ? 1 : 0) | (tts_any_sampling(t) ? 2 : 0),
+                            [&] { return tts_group_body(t, gs, grp, run_dep); });
+      }))
+    return rc;
+  if (int rc = join_groups(e, st, Gn)) return rc;  // only after every group was launched
   if (decode) {  // the entry is queued whatever happens: a slot can emit from step text_audio_delay + acoustic_delay on
     dsm_tts::PcmEntry& en = t->pcm_q[fsel];
     en.launched = false;
@@ -786,9 +697,9 @@ int dsm_tts_attach_mimi(dsm_tts* t, const dsm_mimi_config* mimi, const char* mim
     if (!t) g_create_error = "null argument";
     return DSM_ERR_INVALID;
   }
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   const dsm_tts_config& c = t->cfg;
-  if (t->mimi) { e->set_error("a Mimi is attached already"); return DSM_ERR_STATE; }
+  if (t->mimi || t->dec.ready) { e->set_error("a Mimi is attached already"); return DSM_ERR_STATE; }  // (or got as far as its decode state)
   // srv/tts.rs:309-310: mimi::load(.., Some(audio_codebooks)); every generated token must be a codebook entry
   if (mimi->quantizer_n_q != c.dep_num_slices || mimi->quantizer_bins < c.audio_vocab_size - 1) {
     e->set_error("Mimi with n_q %d / %d bins does not decode frames of %d codebooks with tokens below %d", mimi->quantizer_n_q,
@@ -802,19 +713,19 @@ int dsm_tts_attach_mimi(dsm_tts* t, const dsm_mimi_config* mimi, const char* mim
   dsm_st_file* f = dsm_st_open(mimi_safetensors, err, sizeof err);
   if (!f) { e->set_error("%s", err); return DSM_ERR_IO; }
   Loader ld{e, f};
-  int rc = load_mimi(e, ld, &e->mimi_w, *mimi);
+  int rc = load_mimi(e, ld, &t->mimi_w, *mimi);
   dsm_st_close(f);
   if (rc) return rc;
-  if (!e->mimi_w.has_decoder) { e->set_error("the Mimi checkpoint has no decoder.* tensors"); return DSM_ERR_STATE; }
+  if (!t->mimi_w.has_decoder) { e->set_error("the Mimi checkpoint has no decoder.* tensors"); return DSM_ERR_STATE; }
   const int B = t->B;
-  if ((rc = alloc_dec_state(e))) return rc;
-  if (e->dec.h_descs.empty()) { e->set_error("a decoder without streaming convolutions is not supported"); return DSM_ERR_INVALID; }
-  if ((rc = e->dalloc(&e->dec.started, B))) return rc;
-  HIPCHK(hipEventCreateWithFlags(&t->ev_frames, hipEventDisableTiming));
+  if ((rc = alloc_dec_state(e, t->mimi_w, t->dec, B))) return rc;
+  if (t->dec.h_descs.empty()) { e->set_error("a decoder without streaming convolutions is not supported"); return DSM_ERR_INVALID; }
+  if ((rc = e->dalloc(&t->dec.started, B))) return rc;
+  if ((rc = e->new_event(&t->ev_frames))) return rc;
   for (dsm_tts::PcmEntry& en : t->pcm_q) {
-    HIPCHK(hipEventCreateWithFlags(&en.ev, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc((void**)&en.h_pcm, sizeof(float) * (size_t)B * DSM_FRAME_SIZE));
-    HIPCHK(hipHostMalloc((void**)&en.h_valid, (size_t)B));
+    if ((rc = e->new_event(&en.ev))) return rc;
+    if ((rc = e->halloc(&en.h_pcm, (size_t)B * DSM_FRAME_SIZE))) return rc;
+    if ((rc = e->halloc(&en.h_valid, (size_t)B))) return rc;
   }
   HIPCHK(hipDeviceSynchronize());
   t->mimi = true;
@@ -824,7 +735,7 @@ int dsm_tts_attach_mimi(dsm_tts* t, const dsm_mimi_config* mimi, const char* mim
 int dsm_tts_step_pcm(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* allowed, const uint8_t* mask,
                      uint32_t* text_token_out, uint32_t* audio_out, float* pcm_out, uint8_t* pcm_valid_out) {
   if (!t || !prev_text_token || !allowed || !mask) return DSM_ERR_INVALID;
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   if (!t->mimi) { e->set_error("dsm_tts_step_pcm needs dsm_tts_attach_mimi first"); return DSM_ERR_STATE; }
   if (pcm_out && t->pcm_pending > 0) {
     e->set_error("%d deferred step(s) wait for dsm_tts_recv_pcm: a serial step would deliver out of order", t->pcm_pending);
@@ -843,7 +754,7 @@ int dsm_tts_step_pcm(dsm_tts* t, const uint32_t* prev_text_token, const int32_t*
 int dsm_tts_recv_pcm(dsm_tts* t, float* pcm_out, uint8_t* pcm_valid_out) {
   if (!t) return DSM_ERR_INVALID;
   if (t->pcm_pending == 0) return 0;
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   if (int rc = tts_deliver_pcm(t, pcm_out, pcm_valid_out)) return rc;
@@ -855,7 +766,7 @@ int dsm_tts_pcm_pending(dsm_tts* t) { return t ? t->pcm_pending : DSM_ERR_INVALI
 int dsm_tts_get_metrics(dsm_tts* t, dsm_metrics* out) {
   if (!t || !out) return DSM_ERR_INVALID;
   memset(out, 0, sizeof *out);
-  fill_graph_metrics(t->eng, out);
+  t->fill_graph_metrics(out);
   // algorithmic bytes of one step: every DISTINCT weight matrix the step multiplies by, once (main LM layers + text linear; the
   // stacked depformer input projections; the depformer's shared attention weights, the gating weights of each of its G weight
   // groups and the 32 output linears), bf16.  A weight group serves ~3 consecutive slices and fits the Infinity Cache, so one
@@ -894,7 +805,7 @@ int dsm_tts_step_idx(dsm_tts* t, int slot) {
 
 int dsm_tts_set_sampling(dsm_tts* t, int slot, int top_k, float temperature, uint64_t seed) {
   if (!t || slot < 0 || slot >= t->B) return DSM_ERR_INVALID;
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   // srv/tts.rs:401-408: ArgMax unless temperature > 0 and top_k > 1
@@ -921,7 +832,7 @@ namespace {
 // compute_kv(CaSrc::Tokens(src)) of one batch row into its block of every layer's source cache (core/transformer.rs:299-318)
 template <typename KVT>
 int tts_project_ca_row(dsm_tts* t, hipStream_t st, int row, const float* src, int n) {
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   const dsm_tts_config& c = t->cfg;
   const int d = c.lm.d_model, H = c.lm.num_heads, hd = d / H, kvd = c.ca_dim > 0 ? c.ca_dim : d, smax = t->ca.smax;
   HIPCHK(hipMemcpyAsync(t->ca_src_dev, src, sizeof(float) * (size_t)n * kvd, hipMemcpyHostToDevice, st));
@@ -943,7 +854,7 @@ extern "C" {
 
 int dsm_tts_set_ca_src(dsm_tts* t, int slot, const float* ca_src, int n, const float* ca_src_uncond, int n_uncond, double cfg_alpha) {
   if (!t || slot < 0 || slot >= t->B) return DSM_ERR_INVALID;
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   const dsm_tts_config& c = t->cfg;
   if (!c.cross_attention) { e->set_error("this engine was created without cross_attention"); return DSM_ERR_STATE; }
   if (n < 0 || n_uncond < 0 || n > c.ca_max_len || n_uncond > c.ca_max_len) {
@@ -971,7 +882,7 @@ int dsm_tts_set_ca_src(dsm_tts* t, int slot, const float* ca_src, int n, const f
     const int row = slot * t->rps + j, len = j == 0 ? n : n_uncond;
     const float* src = j == 0 ? ca_src : ca_src_uncond;
     if (len > 0) {
-      const int rc = c.kv_bf16 ? tts_project_ca_row<uint16_t>(t, st, row, src, len) : tts_project_ca_row<float>(t, st, row, src, len);
+      const int rc = with_kv_type(c.kv_bf16 != 0, [&](auto kv) { return tts_project_ca_row<decltype(kv)>(t, st, row, src, len); });
       if (rc) return rc;
       HIPCHK(hipStreamSynchronize(st));  // the staging buffers are reused by the next row; `src` is the caller's memory
     } else if (t->ca_len[row] > 0) {
@@ -1000,7 +911,7 @@ int dsm_tts_reset_slot(dsm_tts* t, int slot) {
     if (int rc = dsm_tts_set_sampling(t, slot, 0, 0.0f, 0)) return rc;
   if (t->cfg.cross_attention)  // ... and whatever ca_src / cfg_alpha its creator passes: none until dsm_tts_set_ca_src
     if (int rc = dsm_tts_set_ca_src(t, slot, nullptr, 0, nullptr, 0, 0.0)) return rc;
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   dsm_tts::Item& it = t->items[slot];
   it.step_idx = 0;
   it.consecutive_pads = 0;
@@ -1015,26 +926,14 @@ int dsm_tts_reset_slot(dsm_tts* t, int slot) {
     // The slot's next generation decodes with a fresh Mimi (srv/tts.rs:499-500: clone() + reset_state()): conv states and carries
     // zero, not started, and — unlike Mimi::reset_batch_idx — the decoder transformer back at position 0.  On the decode stream,
     // i.e. behind the decodes already queued for the old generation.
-    hipStream_t sd = e->s_enc;
-    MimiDecState& d = e->dec;
-    const MimiW& w = e->mimi_w;
-    hipLaunchKernelGGL(conv_state_reset_kernel, dim3((unsigned)d.h_descs.size()), dim3(256), 0, sd, d.descs, slot);
-    HIPCHK(hipGetLastError());
-    for (size_t i = 0; i < w.dec_stages.size(); ++i) {
-      const size_t n = (size_t)(w.dec_stages[i].k - w.dec_stages[i].stride) * w.dec_stages[i].out_c;
-      HIPCHK(hipMemsetAsync(d.stages[i].carry + (size_t)slot * n, 0, n * sizeof(float), sd));
-    }
-    const size_t n = (size_t)w.cfg.downsample_stride * w.cfg.dimension;
-    HIPCHK(hipMemsetAsync(d.up_carry + (size_t)slot * n, 0, n * sizeof(float), sd));
-    HIPCHK(hipMemsetAsync(d.started + slot, 0, 1, sd));
-    if (int rc = reset_transformer_slot(e, sd, d.tr, slot)) return rc;
+    return reset_decoder_slot(e, t->mimi_w, t->dec, e->s_enc, slot, true);
   }
   return 0;
 }
 
 int dsm_tts_debug_read(dsm_tts* t, const char* name, float* out, size_t cap) {
   if (!t || !name || !out) return DSM_ERR_INVALID;
-  dsm_engine* e = t->eng;
+  DsmDevice* e = t;
   const float* src = nullptr;
   size_t n = 0;
   if (!strcmp(name, "lm.hidden")) { src = t->hidden; n = (size_t)t->R * t->cfg.lm.d_model; }
