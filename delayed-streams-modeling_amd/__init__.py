@@ -133,6 +133,7 @@ ABI_SYMBOLS = [
     "dsm_tts_config_v202501", "dsm_tts_create", "dsm_tts_destroy", "dsm_tts_last_error", "dsm_tts_step",
     "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot", "dsm_tts_debug_read", "dsm_tts_get_metrics", "dsm_tts_set_sampling",
     "dsm_tts_set_ca_src", "dsm_tts_attach_mimi", "dsm_tts_step_pcm", "dsm_tts_recv_pcm", "dsm_tts_pcm_pending",
+    "dsm_tts_attach_speaker_encoder", "dsm_tts_encode_voice", "dsm_tts_speaker_empty",
 ]
 PROF_TAGS = ["attn_lm", "gemm_lm", "attn_mimi", "gemm_mimi", "rvq", "other"]
 
@@ -270,6 +271,9 @@ def load_library(path=None):
     lib.dsm_tts_step_pcm.argtypes = [vp, vp, vp, vp, vp, vp, fp, u8p]
     lib.dsm_tts_recv_pcm.argtypes = [vp, fp, u8p]
     lib.dsm_tts_pcm_pending.argtypes = [vp]
+    lib.dsm_tts_attach_speaker_encoder.argtypes = [vp, C.c_int, C.c_char_p]
+    lib.dsm_tts_encode_voice.argtypes = [vp, fp, C.c_int, C.c_int, fp, C.c_int, C.POINTER(C.c_int)]
+    lib.dsm_tts_speaker_empty.argtypes = [vp, fp, C.c_int, C.POINTER(C.c_int)]
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
         getattr(lib, name).restype = C.c_int
@@ -861,6 +865,7 @@ class TtsEngine:
     def __init__(self, cfg, batch_size, lm_path, device_id=0):
         self.lib = load_library()
         self.cfg, self.B, self.S = cfg, batch_size, cfg.dep_num_slices
+        self.n_speakers = 0  # set by attach_speaker_encoder
         h = C.c_void_p()
         rc = self.lib.dsm_tts_create(C.byref(cfg), device_id, batch_size, lm_path.encode(), C.byref(h))
         if rc != 0:
@@ -947,6 +952,29 @@ class TtsEngine:
     def set_sampling(self, slot, top_k, temperature, seed):
         """Sampling::TopK{k, temperature} seeded with `seed` for the slot's text and audio processors (srv/tts.rs:401-415)."""
         self._check(self.lib.dsm_tts_set_sampling(self.h, slot, top_k, temperature, seed))
+
+    def attach_speaker_encoder(self, n_speakers, lm_path):
+        """SpeakerEncoder::new on the attached Mimi (core/tts_streaming.rs:346-372): output_proj and learnt_padding from lm_path."""
+        self._check(self.lib.dsm_tts_attach_speaker_encoder(self.h, n_speakers, lm_path.encode()))
+        self.n_speakers = n_speakers
+
+    def encode_voice(self, clips):
+        """SpeakerEncoder::encode: clips [n_clips][clip_len] f32 at 24 kHz -> ca_src rows [n_speakers * clip_len / 1920][cond_dim]."""
+        a = np.ascontiguousarray(clips, dtype=np.float32)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        cond = self.cfg.ca_dim or self.cfg.lm.d_model
+        cap = max(1, self.n_speakers * (a.shape[1] // FRAME_SIZE))
+        out, rows = np.zeros((cap, cond), dtype=np.float32), C.c_int(0)
+        self._check(self.lib.dsm_tts_encode_voice(self.h, _ptr(a), a.shape[0], a.shape[1], _ptr(out), cap, C.byref(rows)))
+        return out[:rows.value]
+
+    def speaker_empty(self):
+        """SpeakerEncoder::empty: the unconditional source of a guided request, [n_speakers * 125][cond_dim]."""
+        cond = self.cfg.ca_dim or self.cfg.lm.d_model
+        cap = max(1, self.n_speakers * 125)
+        out, rows = np.zeros((cap, cond), dtype=np.float32), C.c_int(0)
+        self._check(self.lib.dsm_tts_speaker_empty(self.h, _ptr(out), cap, C.byref(rows)))
+        return out[:rows.value]
 
     def set_ca_src(self, slot, ca_src, ca_src_uncond=None, cfg_alpha=0.0):
         """State::new's ca_src / cfg_alpha for the slot (srv/tts.rs:426-441): ca_src [n][ca_dim] f32 or None;

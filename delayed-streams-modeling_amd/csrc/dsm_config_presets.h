@@ -100,8 +100,9 @@ static inline void dsm_preset_tts_v202501(dsm_tts_config* c) {
   c->kv_bf16 = 1;
   /* core/lm.rs:392-396 tts_202501: cross_attention = Some((CrossAttentionGating::Normal, NormType::LayerNorm, None)), and the
    * server always builds its State with Some(CaSrc::Tokens(..)) (srv/tts.rs:426-441): the preset carries the branch the
-   * reference runs.  Sources: speaker_cond_n_speakers = 5 x 25 rows at 12.5 Hz -> 125 rows; 128 fit.  Guidance
-   * (two batch rows per slot, cfg_alpha) stays opt-in through cfg_rows, as it is per request in the reference. */
+   * reference runs.  Sources: the server's speaker encoder emits speaker_cond_n_speakers = 5 x 125 rows (10 s
+   * clips at 12.5 Hz) = 625 rows, so a real deployment sets ca_max_len >= 625; the 128 below is this preset's historical value.
+   * Guidance (two batch rows per slot, cfg_alpha) stays opt-in through cfg_rows, as it is per request in the reference. */
   c->cross_attention = 1; c->ca_norm = 0; c->ca_dim = 0; c->ca_max_len = 128; c->cfg_rows = 0;
   c->dot_mode = 1; /* as the STT presets */
 }

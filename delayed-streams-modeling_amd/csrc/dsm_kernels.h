@@ -2346,6 +2346,183 @@ __global__ void tts_frame_kernel(TtsFrameArgs a) {
   a.valid[(long)sel * a.valid_stride + b] = ok ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// Speaker encoder (dsm_speaker.inc): the whole-clip, non-streaming Mimi encode of SpeakerEncoder::encode —
+// core/tts_streaming.rs:382-409.  Tolerance-pinned, not bit-pinned: the oracle has only the streaming Mimi.
+// ------------------------------------------------------------------------------------------
+
+// A block-wide f64 sum in a fixed order: every thread's chain (elements tid, tid + 1024, ...), an xor butterfly inside each
+// wave, the 16 wave totals left to right.  `red` holds 16 doubles; every thread returns the total.
+__device__ __forceinline__ double spk_block_sum(double v, double* red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
+  __syncthreads();  // the previous total has been read by everyone
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = red[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = t + red[w];
+  return t;
+}
+
+// pcm * 0.08 / sqrt(mean((pcm - mean(pcm))^2)) per clip (:388-389; the output is not mean-subtracted).  One workgroup of 1024
+// threads per clip: mean, then the mean squared deviation, both summed in f64 in the order above (the same bits every run), then
+// the f32 product and quotient of the reference.  The scaled clip goes straight into the first convolution's concat buffer
+// behind its zero left pad (out + clip * out_stride); the f32 standard deviation goes to stdev[clip] for the host's check, and a
+// clip whose deviation is zero or not finite is left unscaled (the call fails before anything reads it).
+__global__ __launch_bounds__(1024) void spk_normalize_kernel(const float* __restrict__ pcm, int n, float* __restrict__ out,
+                                                             long out_stride, float* __restrict__ stdev) {
+  __shared__ double red[16];
+  const int clip = blockIdx.x;
+  const float* x = pcm + (long)clip * n;
+  float* y = out + (long)clip * out_stride;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) s = s + (double)x[i];
+  const double mean = spk_block_sum(s, red) / (double)n;
+  double q = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const double dv = (double)x[i] - mean;
+    q = DSM_FMA(dv, dv, q);
+  }
+  const float sd = (float)sqrt(spk_block_sum(q, red) / (double)n);
+  if (threadIdx.x == 0) stdev[clip] = sd;
+  const bool ok = sd > 0.0f && sd < DSM_INF_F;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) y[i] = ok ? (x[i] * 0.08f) / sd : x[i];
+}
+
+// (cos, sin) of (pos0 + t) * inv_freq[i] for t < T: the table the streaming encoder's kv_builder_kernel writes per step, for the
+// whole clip at once.  pos0 = frames per step where the batched transformer reads its positions after the builder advanced them
+// (0 with rope_pos_before).
+__global__ void spk_rope_table_kernel(float* __restrict__ cs, const float* __restrict__ inv_freq, int T, int half, int pos0) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= T * half) return;
+  const int t = e / half, i = e % half;
+  float s, c;
+  dsm_sincosf((float)(uint32_t)(pos0 + t) * inv_freq[i], &s, &c);
+  cs[2 * (long)e] = c;
+  cs[2 * (long)e + 1] = s;
+}
+
+// Causal self-attention over a whole sequence: softmax(rope(q) . rope(k)^T / sqrt(HD) + causal mask) . v for the T positions of
+// one clip.  qkv [clips * T][3 d] is the plain in_proj product (q | k | v, heads inside each — core/batched_transformer.rs:77-82);
+// out [clips * T][d] is what out_proj reads.  One workgroup = SPK_QB = 16 queries of one (clip, head):
+//   1. the 16 queries, rotated (rope_i on interleaved pairs, cs [T][HD / 2][2]), into LDS;
+//   2. keys 0 .. last query of the block in tiles of 64 rows: rotated on load into LDS (row stride HD + 1: the 16 keys a half-wave
+//      reads sit on 16 different banks), thread (query tid / 16, key lane tid % 16) chains its four keys' dot products over
+//      the head dim and stores score * scale, or -inf behind the diagonal, in sc [16][Tp];
+//   3. softmax per query by its 16 lanes: lane chains of max, exp and sum over keys lane, lane + 16, ..., a 16-lane xor
+//      butterfly, the weights divided by the sum once;
+//   4. value tiles of 64 rows into LDS, thread (query, dims lane + 16 i) chains weight * v over the keys in ascending order.
+// Every sum has one order that depends on T alone.  cs null: no positional embedding inside the transformer, q and k are used as
+// they are.  K and V of one head at T = 250, HD = 64 are 128 KB: they pass through a 16.6 KB tile instead, so the launch stays
+// inside the default 64 KB of dynamic LDS up to T = 700 at HD = 64 (860 at HD = 32; spk_attn_lds); attach refuses a longer context.
+#define SPK_QB 16
+#define SPK_KT 64
+template <int HD>
+__host__ __device__ constexpr size_t spk_attn_lds(int T) {
+  return sizeof(float) * ((size_t)SPK_QB * HD + (size_t)SPK_KT * (HD + 1) + (size_t)SPK_QB * ((T + 3) & ~3));
+}
+template <int HD>
+__global__ __launch_bounds__(256) void spk_attn_kernel(float* __restrict__ out, const float* __restrict__ qkv,
+                                                       const float* __restrict__ cs, int T, int H) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int d = H * HD, Tp = (T + 3) & ~3;
+  float* qs = lds;                      // [16][HD]
+  float* kv = qs + SPK_QB * HD;         // [64][HD + 1]: a key tile, later a value tile
+  float* sc = kv + SPK_KT * (HD + 1);   // [16][Tp]
+  const int tid = threadIdx.x, h = blockIdx.y, clip = blockIdx.z;
+  const int q0 = blockIdx.x * SPK_QB;
+  const int nq = min(SPK_QB, T - q0), nkeys = q0 + nq;  // keys 0 .. nkeys - 1 are visible to some query of the block
+  const float* base = qkv + (long)clip * T * 3 * d + h * HD;
+  const float scale = (float)(1.0 / sqrt((double)HD));
+  // a rotated row tile: rows [r0, r0 + nr) of part (0 q, 1 k) into dst with row stride ld
+  auto load_rot = [&](float* dst, int ld, int part, int r0, int nr) {
+    for (int e = tid; e < nr * (HD / 2); e += 256) {
+      const int r = e / (HD / 2), p = e % (HD / 2);
+      const float2 x = *reinterpret_cast<const float2*>(base + (long)(r0 + r) * 3 * d + part * d + 2 * p);
+      const float2 c = cs ? *reinterpret_cast<const float2*>(cs + ((long)(r0 + r) * (HD / 2) + p) * 2) : make_float2(1.0f, 0.0f);
+      const float t0 = x.x * c.x, t1 = x.y * c.y, t2 = x.x * c.y, t3 = x.y * c.x;
+      dst[r * ld + 2 * p] = t0 - t1;
+      dst[r * ld + 2 * p + 1] = t2 + t3;
+    }
+  };
+  load_rot(qs, HD, 0, q0, nq);
+  const int qi = tid >> 4, kl = tid & 15;
+  const int qpos = q0 + qi;  // (rows qi >= nq compute on stale LDS and are never stored)
+  for (int k0 = 0; k0 < nkeys; k0 += SPK_KT) {
+    const int nk = min(SPK_KT, nkeys - k0);
+    __syncthreads();  // the previous tile has been consumed (first pass: nothing to wait for but qs' writers)
+    load_rot(kv, HD + 1, 1, k0, nk);
+    __syncthreads();
+    if (qi < nq) {
+#pragma unroll
+      for (int u = 0; u < SPK_KT / 16; ++u) {
+        const int jl = kl + 16 * u, j = k0 + jl;
+        if (jl < nk) {
+          float p = 0.0f;
+#pragma unroll 8
+          for (int dd = 0; dd < HD; ++dd) p = DSM_FMAF(qs[qi * HD + dd], kv[jl * (HD + 1) + dd], p);
+          sc[qi * Tp + j] = j <= qpos ? p * scale : -DSM_INF_F;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (qi < nq) {  // softmax_last_dim over keys 0 .. nkeys - 1 (exp(-inf - m) = 0: the masked keys weigh nothing)
+    float* row = sc + qi * Tp;
+    float m = -DSM_INF_F;
+    for (int j = kl; j < nkeys; j += 16) m = fmaxf(m, row[j]);
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    float s = 0.0f;
+    for (int j = kl; j < nkeys; j += 16) {
+      const float p = dsm_expf(row[j] - m);
+      row[j] = p;
+      s = s + p;
+    }
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
+    for (int j = kl; j < nkeys; j += 16) row[j] = row[j] / s;
+  }
+  float acc[HD / 16];
+#pragma unroll
+  for (int i = 0; i < HD / 16; ++i) acc[i] = 0.0f;
+  for (int k0 = 0; k0 < nkeys; k0 += SPK_KT) {
+    const int nk = min(SPK_KT, nkeys - k0);
+    __syncthreads();  // the weights are final / the previous value tile has been consumed
+    for (int e = tid; e < nk * (HD / 4); e += 256) {
+      const int r = e / (HD / 4), c4 = 4 * (e % (HD / 4));
+      const float4 v = *reinterpret_cast<const float4*>(base + (long)(k0 + r) * 3 * d + 2 * d + c4);
+      float* dst = kv + r * (HD + 1) + c4;
+      dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+    }
+    __syncthreads();
+    if (qi < nq) {
+      const float* w = sc + qi * Tp + k0;
+      for (int j = 0; j < nk; ++j) {
+        const float wj = w[j];
+#pragma unroll
+        for (int i = 0; i < HD / 16; ++i) acc[i] = DSM_FMAF(wj, kv[j * (HD + 1) + kl + 16 * i], acc[i]);
+      }
+    }
+  }
+  if (qi < nq) {
+    float* o = out + ((long)clip * T + qpos) * d + h * HD;
+#pragma unroll
+    for (int i = 0; i < HD / 16; ++i) o[kl + 16 * i] = acc[i];
+  }
+}
+
+// Rows [row0, row0 + nrows) of a source [rows][dim] = learnt_padding + pos_emb[row]: the speakers a request does not name
+// (core/tts_streaming.rs:397-403) and SpeakerEncoder::empty (:411-416).  zeros_like + learnt_padding is the padding itself
+// (+0 + x = x), then add_sin_embeddings' one f32 add.
+__global__ void spk_pad_rows_kernel(float* __restrict__ rows, const float* __restrict__ pad, const float* __restrict__ pos, long row0,
+                                    long nrows, int dim) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nrows * dim) return;
+  const long at = row0 * dim + e;
+  rows[at] = (0.0f + pad[e % dim]) + pos[at];
+}
+
 __global__ void fill_u32_kernel(uint32_t* p, uint32_t v, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;

@@ -18,6 +18,30 @@ struct DepW {
   std::vector<TransformerW> tr;        // [G] shared attention/norm weights, per-group gating
 };
 
+// SpeakerEncoder (core/tts_streaming.rs:335-417) on the attached Mimi: weights, tables and the whole-clip scratch of
+// dsm_speaker.inc.  None of it is shared with the step or the decode side.
+struct SpkEnc {
+  bool ready = false;
+  int n_speakers = 0, cond_dim = 0;
+  int max_r = 0;     // longest clip in Mimi frames: transformer.context / frames per step at the encoder rate
+  int pos_rows = 0;  // rows of the position table
+  Linear proj;       // output_proj [cond_dim][dimension] f32
+  float *pad = nullptr, *pos = nullptr;  // learnt_padding [cond_dim], pos_emb [pos_rows][cond_dim]
+  float *pcm = nullptr, *stdev = nullptr, *cat_init = nullptr;  // [n_speakers][clip], [n_speakers], [n_speakers][S0 + clip]
+  struct Stage {
+    float *y = nullptr, *cat_ra = nullptr, *cat_rb = nullptr, *cat_down = nullptr;  // one clip
+  };
+  std::vector<Stage> stages;
+  float* cat_final = nullptr;  // one clip
+  float *x = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *ff = nullptr, *rope_cs = nullptr;  // [n_speakers * T] rows
+  float *cat_ds = nullptr, *latent = nullptr, *rows = nullptr;
+  float *h_stdev = nullptr, *h_rows = nullptr;  // pinned
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;    // device time of the last encode
+  size_t scratch_bytes = 0;
+  int last_c = 0, last_r = 0;  // shape of the last encode ("spk.*" taps)
+  float last_ms = 0.0f;
+};
+
 }  // namespace
 
 struct dsm_tts : DsmDevice {
@@ -93,6 +117,7 @@ struct dsm_tts : DsmDevice {
   PcmEntry pcm_q[2];
   uint64_t pcm_seq = 0;  // step_pcm calls so far: entry / frame buffer of call n is n & 1
   int pcm_pending = 0;   // entries queued and not yet delivered (the oldest is (pcm_seq - pcm_pending) & 1)
+  SpkEnc spk;            // voice clips -> cross-attention rows (dsm_tts_attach_speaker_encoder, dsm_speaker.inc)
 };
 
 namespace {
@@ -547,6 +572,10 @@ int tts_deliver_pcm(dsm_tts* t, float* pcm_out, uint8_t* pcm_valid_out) {
 
 }  // namespace
 
+namespace {
+int spk_debug_read(dsm_tts* t, const char* name, float* out, size_t cap);  // dsm_speaker.inc
+}
+
 extern "C" {
 
 void dsm_tts_config_v202501(dsm_tts_config* out) { dsm_preset_tts_v202501(out); }
@@ -934,6 +963,7 @@ int dsm_tts_reset_slot(dsm_tts* t, int slot) {
 int dsm_tts_debug_read(dsm_tts* t, const char* name, float* out, size_t cap) {
   if (!t || !name || !out) return DSM_ERR_INVALID;
   DsmDevice* e = t;
+  if (!strncmp(name, "spk.", 4)) return spk_debug_read(t, name, out, cap);
   const float* src = nullptr;
   size_t n = 0;
   if (!strcmp(name, "lm.hidden")) { src = t->hidden; n = (size_t)t->R * t->cfg.lm.d_model; }

@@ -152,9 +152,11 @@ def lm_spec(cfg):
     return s
 
 
-def tts_spec(cfg, legacy_ca=False):
+def tts_spec(cfg, legacy_ca=False, speaker=False, mimi_dim=0):
     """TTS checkpoint keys (core/lm.rs:501-590): main LM + shared depformer with per-group gating/linear_in.
-    cfg.cross_attention adds every layer's norm_cross + cross_attention tensors (legacy_ca: the single in_proj_weight layout)."""
+    cfg.cross_attention adds every layer's norm_cross + cross_attention tensors (legacy_ca: the single in_proj_weight layout).
+    speaker: the two SpeakerEncoder tensors (core/tts_streaming.rs:353-362) for a speaker tokenizer of width mimi_dim, appended
+    (every tensor has its own stream, so the other tensors' bytes do not change)."""
     s = Spec()
     t, dp = cfg.lm, cfg.depformer
     d, D, S, G, lr = t.d_model, dp.d_model, cfg.dep_num_slices, cfg.dep_weight_groups, cfg.dep_low_rank
@@ -201,15 +203,23 @@ def tts_spec(cfg, legacy_ca=False):
         for g in range(G):
             s.add(f"{p}.gating.{g}.linear_in.weight", (2 * hid, D), "normal", D ** -0.5)
             s.add(f"{p}.gating.{g}.linear_out.weight", (D, hid), "normal", hid ** -0.5)
+    if speaker:
+        cond = cfg.ca_dim or d
+        p = "condition_provider.conditioners.speaker_wavs"
+        s.add(f"{p}.output_proj.weight", (cond, mimi_dim), "normal", mimi_dim ** -0.5)
+        s.add(f"{p}.learnt_padding", (1, 1, cond), "normal", 0.5)
     return s
 
 
-def make_synth_tts_weights(cfg, out_dir, seed=SEED, tag="tts", legacy_ca=False):
-    """The tag must tell configurations apart (files are cached by name): use e.g. "tts_tiny_ca" with cfg.cross_attention."""
+def make_synth_tts_weights(cfg, out_dir, seed=SEED, tag="tts", legacy_ca=False, speaker=False, mimi_dim=0):
+    """The tag must tell configurations apart (files are cached by name): use e.g. "tts_tiny_ca" with cfg.cross_attention.
+    speaker=True (with the speaker tokenizer's mimi_dim) adds the SpeakerEncoder tensors; the file is <tag>_spk<mimi_dim>."""
     os.makedirs(out_dir, exist_ok=True)
+    if speaker:
+        tag = f"{tag}_spk{mimi_dim}"
     path = os.path.join(out_dir, f"{tag}.lm.safetensors")
     if not os.path.exists(path):
-        write_safetensors(path, tts_spec(cfg, legacy_ca), "BF16", seed)
+        write_safetensors(path, tts_spec(cfg, legacy_ca, speaker, mimi_dim), "BF16", seed)
     return path
 
 

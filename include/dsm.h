@@ -389,6 +389,37 @@ int dsm_tts_step_pcm(dsm_tts*, const uint32_t* prev_text_token, const int32_t* a
                      float* pcm_out /* [B*1920] or NULL = deferred */, uint8_t* pcm_valid_out /* [B] */);
 int dsm_tts_recv_pcm(dsm_tts*, float* pcm_out, uint8_t* pcm_valid_out);
 int dsm_tts_pcm_pending(dsm_tts*);
+/* Voice clips to cross-attention rows — what the reference's server does on every voice-cache miss (srv/tts.rs:702-778,
+ * 946-964) before a request's first step.  The rows go to dsm_tts_set_ca_src: ca_src from dsm_tts_encode_voice, ca_src_uncond
+ * from dsm_tts_speaker_empty (srv/tts.rs:833-838).  Caching them per voice stays with the caller (the reference's
+ * dynamic_ca_srcs cache lives in the server).  cond_dim = ca_dim if non-zero, else lm.d_model.  Rows are f32, the dtype
+ * dsm_tts_set_ca_src takes: the reference's final to_dtype(self.dtype) (bf16 on its GPU path) is NOT applied.
+ *   dsm_tts_attach_speaker_encoder   SpeakerEncoder::new — core/tts_streaming.rs:346-372, srv/tts.rs:311-333.  The speaker
+ *     tokenizer is the Mimi attached with dsm_tts_attach_mimi, as in the shipped configuration (configs/tts/config-tts.toml:17-18
+ *     names one file twice).  Reads condition_provider.conditioners.speaker_wavs.{output_proj.weight [cond_dim][dimension],
+ *     learnt_padding [1,1,cond_dim]} (BF16 or F32, kept as f32) from lm_safetensors and allocates the clip path's scratch for
+ *     clips of up to transformer.context / downsample_stride frames.  DSM_ERR_STATE without a Mimi, without cfg.cross_attention
+ *     or when attached already; DSM_ERR_IO for a missing key or a wrong shape; DSM_ERR_INVALID for n_speakers < 1.
+ *   dsm_tts_encode_voice   SpeakerEncoder::encode — core/tts_streaming.rs:382-409 on the slices the caller has made
+ *     (srv/tts.rs:946-964): every clip is scaled to x * 0.08 / stddev(x), encoded by a whole-clip (non-streaming) Mimi encode
+ *     (Mimi::encode_pre_quantize, core/mimi.rs:177-183) and projected.  pcm: host [n_clips][clip_len] at 24 kHz, clips beyond
+ *     n_speakers are ignored.  clip_len must be a positive multiple of DSM_FRAME_SIZE with clip_len / DSM_FRAME_SIZE *
+ *     downsample_stride <= transformer.context (the shipped 10 s clip: 240 000 samples = 250 positions).  With r = clip_len /
+ *     1920 and c = min(n_clips, n_speakers) the result is n_speakers * r rows: c * r projected rows, speaker-major, then
+ *     (n_speakers - c) * r copies of learnt_padding; row j of the whole gets add_sin_embeddings' pos_emb[j] (core/tts.rs:94-109).
+ *     *rows_out is set whenever the clip shape is valid; DSM_ERR_INVALID for n_clips < 1 ("empty speakers in encode"), a bad
+ *     clip_len, cap_rows < rows, or a clip whose standard deviation is zero or not finite (the reference would hand NaNs to the
+ *     LM).  Synchronous, on the model stream between steps, like dsm_tts_set_ca_src; a generation in progress is not disturbed.
+ *     Tolerance-pinned against the streaming oracle; two calls with the same input return identical bytes.
+ *   dsm_tts_speaker_empty  SpeakerEncoder::empty — core/tts_streaming.rs:411-416: n_speakers * 125 rows of learnt_padding +
+ *     pos_emb (the 125 is the reference's literal, whatever the clip length).
+ * dsm_tts_debug_read taps: "spk.pcm_norm" [c][clip_len], "spk.latent" [c * r][dimension] (encode_pre_quantize transposed) of the
+ * last encode; "spk.stats" = {scratch MiB, milliseconds between events around that encode's enqueue, the host's wait for the
+ * standard deviations included}; "spk.launches" = {kernel launches of that encode's device side: kernel nodes of a discarded capture}. */
+int dsm_tts_attach_speaker_encoder(dsm_tts*, int n_speakers, const char* lm_safetensors);
+int dsm_tts_encode_voice(dsm_tts*, const float* pcm /* host [n_clips][clip_len], 24 kHz */, int n_clips, int clip_len,
+                         float* ca_src_out /* host [rows][cond_dim] */, int cap_rows, int* rows_out);
+int dsm_tts_speaker_empty(dsm_tts*, float* ca_src_out, int cap_rows, int* rows_out);
 int dsm_tts_debug_read(dsm_tts*, const char* name, float* out, size_t cap); /* "lm.hidden", "lm.logits": one row per BATCH ROW (2 per slot with cfg_rows) */
 int dsm_tts_get_metrics(dsm_tts*, dsm_metrics* out); /* graph_launches / eager_bodies only */
 
