@@ -78,6 +78,13 @@ struct ConvGeom {
   bool replicate = false;
 };
 
+ConvGeom over_frames(const ConvGeom& g, int r) {  // the streaming geometry of one frame, over r frames at once
+  ConvGeom c = g;
+  c.T_in *= r;
+  c.T_out *= r;
+  return c;
+}
+
 struct TLayerW {
   Linear in_proj, out_proj, ff_in, ff_out;
   float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr, *ls1 = nullptr, *ls2 = nullptr;
@@ -145,15 +152,27 @@ struct MimiW {
   const float** emb_ptrs = nullptr;  // device array of n_q codebook pointers
 };
 
-struct MimiState {  // one per side (encoder-thread clone / model side)
-  float* pcm = nullptr;  // == cat_init + S0 (the PCM frame is uploaded straight into the concat buffer)
+// The activation scratch of one transformer_forward: x (in / out), xn, q, att [rows][d] and g [rows][hidden]
+struct ActScratch {
+  float *x = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *g = nullptr;
+  ActScratch from_row(size_t r0, int d, int hid) const { return {x + r0 * d, xn + r0 * d, q + r0 * d, att + r0 * d, g + r0 * hid}; }
+};
+
+// The buffers of the SEANet encoder chain (alloc_seanet_enc, seanet_encode): the concat buffer in front of every convolution
+// and each stage's skip input y.  The streaming encoder holds them for B slots of one frame, the clip encoder for one clip.
+struct SeanetEnc {
   float* cat_init = nullptr;
   struct Stage {
     float *y = nullptr, *cat_ra = nullptr, *cat_rb = nullptr, *cat_down = nullptr;
   };
   std::vector<Stage> stages;
   float* cat_final = nullptr;
-  float *x_tr = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *ff = nullptr;
+};
+
+struct MimiState {  // one per side (encoder-thread clone / model side)
+  float* pcm = nullptr;  // == enc.cat_init + S0 (the PCM frame is uploaded straight into the concat buffer)
+  SeanetEnc enc;
+  ActScratch act;  // the encoder transformer's
   float* cat_ds = nullptr;
   float* latent = nullptr;
   float *res_first = nullptr, *res_rest = nullptr, *pval = nullptr;
@@ -177,7 +196,7 @@ struct MimiDecState {  // Mimi::decode_step state, allocated on first use
   // flag instead of first_call (null: module-level first call, Mimi::decode_step of one batched module)
   uint8_t* started = nullptr;
   float *q_first = nullptr, *q_rest = nullptr, *emb = nullptr, *up_carry = nullptr;
-  float *x_tr = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *ff = nullptr;
+  ActScratch act;  // the decoder transformer's
   TransformerState tr;
   float* cat_init = nullptr;
   struct Stage {
@@ -196,12 +215,6 @@ struct LmW {
   TransformerW tr;
   float* out_norm = nullptr;
   Linear text_linear, extra_heads;
-};
-
-// The activation scratch of one LM transformer_forward: x (in / out), xn, q, att [rows][d] and g [rows][hidden]
-struct ActScratch {
-  float *x = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *g = nullptr;
-  ActScratch from_row(size_t r0, int d, int hid) const { return {x + r0 * d, xn + r0 * d, q + r0 * d, att + r0 * d, g + r0 * hid}; }
 };
 
 struct LmState {
@@ -743,8 +756,7 @@ int alloc_cat(DsmDevice* e, float** out, const ConvGeom& c, int B) {
   return e->dalloc(out, (size_t)B * (c.S + c.T_in) * c.in_c);
 }
 
-void add_desc(std::vector<ConvStateDesc>& descs, float* cat, const ConvGeom& c) {  // a conv that carries frames between steps
-  if (c.S == 0) return;
+ConvStateDesc conv_desc(float* cat, const ConvGeom& c) {
   ConvStateDesc d;
   d.cat = cat;
   d.bstride = (long)(c.S + c.T_in) * c.in_c;
@@ -752,32 +764,44 @@ void add_desc(std::vector<ConvStateDesc>& descs, float* cat, const ConvGeom& c) 
   d.T = c.T_in;
   d.C = c.in_c;
   d.replicate = c.replicate ? 1 : 0;
-  descs.push_back(d);
+  return d;
+}
+void add_desc(std::vector<ConvStateDesc>& descs, float* cat, const ConvGeom& c) {  // a conv that carries frames between steps
+  if (c.S > 0) descs.push_back(conv_desc(cat, c));
+}
+
+// The SEANet encoder chain's buffers for B items of r frames each; cat_init for n_init items (the clip path keeps every clip's
+// PCM there and runs the chain one clip at a time).  descs: the list the streaming path's carried conv states are appended to;
+// null where nothing is carried.  floats, if given, grows by what was allocated.
+int alloc_seanet_enc(DsmDevice* e, SeanetEnc* s, const MimiW& w, int n_init, int B, int r, std::vector<ConvStateDesc>* descs,
+                     size_t* floats = nullptr) {
+  auto alloc = [&](float** out, size_t count) {
+    if (floats) *floats += count;
+    return e->dalloc(out, count);
+  };
+  auto cat = [&](float** out, const ConvGeom& c, int n) {
+    const ConvGeom g = over_frames(c, r);
+    if (int rc = alloc(out, (size_t)n * (g.S + g.T_in) * g.in_c)) return rc;
+    if (descs) add_desc(*descs, *out, g);
+    return 0;
+  };
+  if (int rc = cat(&s->cat_init, w.init_conv, n_init)) return rc;
+  s->stages.resize(w.stages.size());
+  for (size_t i = 0; i < w.stages.size(); ++i) {
+    const MimiW::Stage& st = w.stages[i];
+    if (int rc = alloc(&s->stages[i].y, (size_t)B * st.ra.T_in * r * st.ra.in_c)) return rc;
+    if (int rc = cat(&s->stages[i].cat_ra, st.ra, B)) return rc;
+    if (int rc = cat(&s->stages[i].cat_rb, st.rb, B)) return rc;
+    if (int rc = cat(&s->stages[i].cat_down, st.down, B)) return rc;
+  }
+  return cat(&s->cat_final, w.final_conv, B);
 }
 
 int alloc_mimi_state(DsmDevice* e, MimiState* s, const MimiW& w, int B) {
   const dsm_mimi_config& cfg = w.cfg;
-  if (int rc = alloc_cat(e, &s->cat_init, w.init_conv, B)) return rc;
-  add_desc(s->h_descs, s->cat_init, w.init_conv);
-  s->stages.resize(w.stages.size());
-  for (size_t i = 0; i < w.stages.size(); ++i) {
-    const MimiW::Stage& st = w.stages[i];
-    if (int rc = e->dalloc(&s->stages[i].y, (size_t)B * st.ra.T_in * st.ra.in_c)) return rc;
-    if (int rc = alloc_cat(e, &s->stages[i].cat_ra, st.ra, B)) return rc;
-    if (int rc = alloc_cat(e, &s->stages[i].cat_rb, st.rb, B)) return rc;
-    if (int rc = alloc_cat(e, &s->stages[i].cat_down, st.down, B)) return rc;
-    add_desc(s->h_descs, s->stages[i].cat_ra, st.ra);
-    add_desc(s->h_descs, s->stages[i].cat_rb, st.rb);
-    add_desc(s->h_descs, s->stages[i].cat_down, st.down);
-  }
-  if (int rc = alloc_cat(e, &s->cat_final, w.final_conv, B)) return rc;
-  add_desc(s->h_descs, s->cat_final, w.final_conv);
+  if (int rc = alloc_seanet_enc(e, &s->enc, w, B, B, 1, &s->h_descs)) return rc;
   const int Tt = w.final_conv.T_out, d = cfg.dimension;
-  if (int rc = e->dalloc(&s->x_tr, (size_t)B * Tt * d)) return rc;
-  if (int rc = e->dalloc(&s->xn, (size_t)B * Tt * d)) return rc;
-  if (int rc = e->dalloc(&s->q, (size_t)B * Tt * d)) return rc;
-  if (int rc = e->dalloc(&s->att, (size_t)B * Tt * d)) return rc;
-  if (int rc = e->dalloc(&s->ff, (size_t)B * Tt * cfg.transformer.dim_feedforward)) return rc;
+  if (int rc = alloc_act(e, &s->act, (size_t)B * Tt, d, cfg.transformer.dim_feedforward)) return rc;  // (hidden, or more with gating)
   if (int rc = alloc_cat(e, &s->cat_ds, w.downsample, B)) return rc;
   s->ds_desc = (int)s->h_descs.size();
   add_desc(s->h_descs, s->cat_ds, w.downsample);
@@ -791,7 +815,7 @@ int alloc_mimi_state(DsmDevice* e, MimiState* s, const MimiW& w, int B) {
   if (int rc = e->dalloc(&s->mask, B)) return rc;
   if (int rc = alloc_transformer_state(e, &s->tr, cfg.transformer, B, Tt, false)) return rc;
   if (int rc = e->upload(&s->descs, s->h_descs.data(), s->h_descs.size())) return rc;
-  s->pcm = s->cat_init + (size_t)w.init_conv.S * w.init_conv.in_c;  // slot 0's frame; slots are bstride apart
+  s->pcm = s->enc.cat_init + (size_t)w.init_conv.S * w.init_conv.in_c;  // slot 0's frame; slots are bstride apart
   return 0;
 }
 

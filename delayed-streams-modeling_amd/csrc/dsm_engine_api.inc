@@ -53,38 +53,117 @@ int launch_attn(DsmDevice* e, hipStream_t st, float* out, const float* q, const 
   return DSM_ERR_INVALID;
 }
 
+float norm_eps(int rms) { return rms ? 1e-8f : 1e-5f; }  // LayerNorm / RmsNorm — core/batched_transformer.rs:236-252
+
 int run_norm(DsmDevice* e, hipStream_t st, float* y, const float* x, const float* w, const float* b, int rows, int d,
              int rms) {
-  hipLaunchKernelGGL(row_norm_kernel, dim3(rows), dim3(256), 0, st, y, x, w, b, rows, d,
-                     rms ? 1e-8f : 1e-5f, rms);
+  hipLaunchKernelGGL(row_norm_kernel, dim3(rows), dim3(256), 0, st, y, x, w, b, rows, d, norm_eps(rms), rms);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-// batched_transformer::StreamingTransformer::forward_ca — core/batched_transformer.rs:425-459
-// x [B*T][d] is updated in place; the last layer's output may be redirected to (final_out, final_map).
-// Every norm except the first is fused behind the GEMM that produces its input (split-K reduce + residual + norm
-// in one row-wise kernel); post_norm_w/post_norm_out optionally append the model's output norm the same way.
+// Layer l of a transformer stack from the point where its self-attention output sits in act.att, for M = B * T rows: out_proj
+// (+ layer scale, residual) with norm2 — or norm_cross and the cross-attention block, then norm2 — the gated or plain FFN, and
+// ff_out with the next layer's norm1.  The last layer's output may be redirected to (final_out, final_map) and followed by the
+// model's output norm (post_norm_w / post_norm_out).  Every norm is fused behind the GEMM that produces its input (split-K reduce
+// + residual + norm in one row-wise kernel).  Written once for both attention fronts: the ring of transformer_forward and the
+// whole-clip attention of spk_encode_body (dsm_speaker.inc).
+template <typename WT, typename KVT>
+int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, int l, const ActScratch& act, int B, int T,
+                           float* final_out, RowMap final_map, const float* post_norm_w, float* post_norm_out, const CaState* ca) {
+  const dsm_transformer_config& c = w.cfg;
+  const int d = c.d_model, H = c.num_heads, hd = d / H, M = B * T;
+  const float eps = norm_eps(c.norm);
+  const TLayerW& L = w.layers[l];
+  const bool last = (l == c.num_layers - 1);
+  {
+    GemmArgs a = base_args(L.out_proj, act.att, plain_map(M, d), M);
+    a.scale = L.ls1;
+    a.res = act.x; a.rmap = plain_map(M, d);
+    a.Y = act.x; a.ymap = plain_map(M, d);
+    if (ca) {  // norm_cross follows instead of norm2 — core/transformer.rs:755-757
+      a.norm_w = L.ncw; a.norm_b = L.ncb; a.norm_out = act.xn; a.norm_eps = norm_eps(w.ca_norm_rms); a.norm_rms = w.ca_norm_rms;
+    } else {
+      a.norm_w = L.n2w; a.norm_b = L.n2b; a.norm_out = act.xn; a.norm_eps = eps; a.norm_rms = c.norm;  // norm2
+    }
+    if (int rc = gemm_store<WT>(e, st, a)) return rc;
+  }
+  if (ca) {  // xs = residual + cross_attn.forward(norm_cross(xs), ca_src) — core/transformer.rs:753-760, :320-352
+    AttnFused none{};
+    none.nt = sizeof(KVT) == 2;  // as for the self-attention (transformer_forward)
+    {
+      GemmArgs a = base_args(L.ca_q, act.xn, plain_map(M, d), M);  // in_proj_q, (b, t, H, hd)
+      a.Y = act.q; a.ymap = plain_map(M, d);
+      // T = 1, split-K, plain epilogue: the ordered slab sum of the query runs in the attention kernel's prologue (r04)
+      a.defer_reduce = (T == 1 && a.Kpad > DSM_KC && a.K % 32 == 0 && !a.bias && d % 4 == 0 && e->fuse_qkv) ? 1 : 0;
+      if (int rc = gemm_store<WT>(e, st, a)) return rc;
+      if (a.defer_reduce) {  // (cleared by the launcher when a workgroup walked the whole K itself)
+        none.ws = a.ws;
+        none.ld = (long)a.ws_ntiles * 16;
+        none.cstride = (long)((M + 15) / 16) * 16 * none.ld;
+        none.chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
+        none.q_only = 1;
+      }
+    }
+    // softmax(q k^T hd^-1/2) v over the row's source, no mask: the self-attention kernel on a "ring" that holds the
+    // projected source, every row of it visible (canonical order as for the ring)
+    if (int rc = launch_attn<KVT>(e, st, ca->att, act.q, ca->k[l], ca->v[l], ca->last, ca->act, B, H, hd, T, ca->smax, d, none)) return rc;
+    GemmArgs a = base_args(L.ca_out, ca->att, plain_map(M, d), M);  // out_proj; gating = Normal
+    a.res = act.x; a.rmap = plain_map(M, d);
+    a.Y = act.x; a.ymap = plain_map(M, d);
+    a.norm_w = L.n2w; a.norm_b = L.n2b; a.norm_out = act.xn; a.norm_eps = eps; a.norm_rms = c.norm;  // norm2
+    if (int rc = gemm_store<WT>(e, st, a)) return rc;
+  }
+  if (c.gating) {  // Mlp::Gating — core/batched_transformer.rs:170-176
+    GemmArgs a = base_args(L.ff_in, act.xn, plain_map(M, d), M);
+    a.N = w.hidden;
+    a.nt_stride = w.hidden;
+    a.Y = act.g; a.ymap = plain_map(M, w.hidden);
+    if (int rc = launch_gemm_t<WT, KVT, EPI_GATE, 2>(e, st, a, true)) return rc;
+  } else {  // Mlp::NoGating — :169
+    GemmArgs a = base_args(L.ff_in, act.xn, plain_map(M, d), M);
+    a.act = 1;
+    a.Y = act.g; a.ymap = plain_map(M, w.hidden);
+    if (int rc = gemm_store<WT>(e, st, a)) return rc;
+  }
+  GemmArgs a = base_args(L.ff_out, act.g, plain_map(M, w.hidden), M);
+  a.scale = L.ls2;
+  a.res = act.x; a.rmap = plain_map(M, d);
+  if (last && final_out) {
+    a.Y = final_out; a.ymap = final_map;
+  } else {
+    a.Y = act.x; a.ymap = plain_map(M, d);
+  }
+  if (!last) {  // the next layer's norm1
+    a.norm_w = w.layers[l + 1].n1w; a.norm_b = w.layers[l + 1].n1b; a.norm_out = act.xn; a.norm_eps = eps; a.norm_rms = c.norm;
+  } else if (post_norm_out) {  // e.g. LmModel::out_norm — core/lm.rs:1002
+    a.norm_w = post_norm_w; a.norm_b = nullptr; a.norm_out = post_norm_out; a.norm_eps = eps; a.norm_rms = c.norm;
+  }
+  return gemm_store<WT>(e, st, a);
+}
+
+// batched_transformer::StreamingTransformer::forward_ca — core/batched_transformer.rs:425-459, the streaming stack
+// act.x [B*T][d] is updated in place; the last layer's output may be redirected to (final_out, final_map).
+// This function's own: the head (ring bookkeeping in kv_builder_kernel, the first norm) and per layer the ring front — the QKV
+// projection that scatters into the ring and the attention over it.  The rest of each layer is transformer_layer_tail, shared
+// with the whole-clip encoder.
 // phase: 0 = the whole stack; 1 = only the head of it — ring bookkeeping, first norm, layer 0's QKV projection and attention
 // (what a stream group runs before it lets the next group start: the staggered start of lm_step); 2 = everything after that.
 template <typename WT, typename KVT>
-int transformer_forward(DsmDevice* e, hipStream_t st, const TransformerW& w, TransformerState& s, float* x, float* xn,
-                        float* q, float* att, float* ff, int B, int T, const uint8_t* d_mask, float* final_out,
-                        RowMap final_map, const float* post_norm_w = nullptr, float* post_norm_out = nullptr, int phase = 0,
-                        const CaState* ca = nullptr, bool head_done = false) {
+int transformer_forward(DsmDevice* e, hipStream_t st, const TransformerW& w, TransformerState& s, const ActScratch& act, int B,
+                        int T, const uint8_t* d_mask, float* final_out, RowMap final_map, const float* post_norm_w = nullptr,
+                        float* post_norm_out = nullptr, int phase = 0, const CaState* ca = nullptr, bool head_done = false) {
   const dsm_transformer_config& c = w.cfg;
   const int d = c.d_model, H = c.num_heads, hd = d / H, M = B * T;
-  const float eps = c.norm == 1 ? 1e-8f : 1e-5f;
   if (phase != 2 && !head_done) {  // head_done: the caller's own kernel did the ring bookkeeping and norm1 of layer 0 (dep_head_kernel)
     hipLaunchKernelGGL(kv_builder_kernel, dim3(B), dim3(64), 0, st, s.pos, s.idx, d_mask, s.start_pos, s.widx,
                        c.positional_embedding == 1 ? s.rope_cs : (float*)nullptr, w.inv_freq, B, T, c.context, hd,
                        w.rope_pos_before ? 1 : 0);
     HIPCHK(hipGetLastError());
-    if (int rc = run_norm(e, st, xn, x, w.layers[0].n1w, w.layers[0].n1b, M, d, c.norm)) return rc;
+    if (int rc = run_norm(e, st, act.xn, act.x, w.layers[0].n1w, w.layers[0].n1b, M, d, c.norm)) return rc;
   }
   for (int l = 0; l < c.num_layers; ++l) {
     const TLayerW& L = w.layers[l];
-    const bool last = (l == c.num_layers - 1);
     AttnFused fq{};
     // Non-temporal K / V loads for the bf16 rings (the LM's): a ring is read once per step and all of them together are far
     // larger than the Infinity Cache, so they should not evict the weights the other stream group reads next.  Measured:
@@ -92,8 +171,8 @@ int transformer_forward(DsmDevice* e, hipStream_t st, const TransformerW& w, Tra
     // stt-2.6b 4704 -> 4560 us; the f32 rings of Mimi (T = 2) get 6-13 % SLOWER with it and keep ordinary loads.
     fq.nt = sizeof(KVT) == 2;
     if (!(phase == 2 && l == 0)) {
-      GemmArgs a = base_args(L.in_proj, xn, plain_map(M, d), M);
-      a.Y = q;
+      GemmArgs a = base_args(L.in_proj, act.xn, plain_map(M, d), M);
+      a.Y = act.q;
       a.d = d; a.hd = hd; a.H = H; a.T = T; a.ctx = c.context;
       a.kcache = s.k[l]; a.vcache = s.v[l];
       a.widx = s.widx;
@@ -111,76 +190,10 @@ int transformer_forward(DsmDevice* e, hipStream_t st, const TransformerW& w, Tra
         fq.rope_cs = a.rope_cs;
         fq.widx = s.widx;
       }
+      if (int rc = launch_attn<KVT>(e, st, act.att, act.q, s.k[l], s.v[l], s.start_pos, d_mask, B, H, hd, T, c.context, d, fq)) return rc;
     }
-    if (!(phase == 2 && l == 0))
-      if (int rc = launch_attn<KVT>(e, st, att, q, s.k[l], s.v[l], s.start_pos, d_mask, B, H, hd, T, c.context, d, fq)) return rc;
     if (phase == 1) return 0;
-    {
-      GemmArgs a = base_args(L.out_proj, att, plain_map(M, d), M);
-      a.scale = L.ls1;
-      a.res = x; a.rmap = plain_map(M, d);
-      a.Y = x; a.ymap = plain_map(M, d);
-      if (ca) {  // norm_cross follows instead of norm2 — core/transformer.rs:755-757
-        a.norm_w = L.ncw; a.norm_b = L.ncb; a.norm_out = xn; a.norm_eps = w.ca_norm_rms ? 1e-8f : 1e-5f; a.norm_rms = w.ca_norm_rms;
-      } else {
-        a.norm_w = L.n2w; a.norm_b = L.n2b; a.norm_out = xn; a.norm_eps = eps; a.norm_rms = c.norm;  // norm2
-      }
-      if (int rc = gemm_store<WT>(e, st, a)) return rc;
-    }
-    if (ca) {  // xs = residual + cross_attn.forward(norm_cross(xs), ca_src) — core/transformer.rs:753-760, :320-352
-      AttnFused none{};
-      none.nt = fq.nt;
-      {
-        GemmArgs a = base_args(L.ca_q, xn, plain_map(M, d), M);  // in_proj_q, (b, t, H, hd)
-        a.Y = q; a.ymap = plain_map(M, d);
-        // T = 1, split-K, plain epilogue: the ordered slab sum of the query runs in the attention kernel's prologue (r04)
-        a.defer_reduce = (T == 1 && a.Kpad > DSM_KC && a.K % 32 == 0 && !a.bias && d % 4 == 0 && e->fuse_qkv) ? 1 : 0;
-        if (int rc = gemm_store<WT>(e, st, a)) return rc;
-        if (a.defer_reduce) {  // (cleared by the launcher when a workgroup walked the whole K itself)
-          none.ws = a.ws;
-          none.ld = (long)a.ws_ntiles * 16;
-          none.cstride = (long)((M + 15) / 16) * 16 * none.ld;
-          none.chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
-          none.q_only = 1;
-        }
-      }
-      // softmax(q k^T hd^-1/2) v over the row's source, no mask: the self-attention kernel on a "ring" that holds the
-      // projected source, every row of it visible (canonical order as for the ring)
-      if (int rc = launch_attn<KVT>(e, st, ca->att, q, ca->k[l], ca->v[l], ca->last, ca->act, B, H, hd, T, ca->smax, d, none)) return rc;
-      GemmArgs a = base_args(L.ca_out, ca->att, plain_map(M, d), M);  // out_proj; gating = Normal
-      a.res = x; a.rmap = plain_map(M, d);
-      a.Y = x; a.ymap = plain_map(M, d);
-      a.norm_w = L.n2w; a.norm_b = L.n2b; a.norm_out = xn; a.norm_eps = eps; a.norm_rms = c.norm;  // norm2
-      if (int rc = gemm_store<WT>(e, st, a)) return rc;
-    }
-    if (c.gating) {  // Mlp::Gating — core/batched_transformer.rs:170-176
-      GemmArgs a = base_args(L.ff_in, xn, plain_map(M, d), M);
-      a.N = w.hidden;
-      a.nt_stride = w.hidden;
-      a.Y = ff; a.ymap = plain_map(M, w.hidden);
-      if (int rc = launch_gemm_t<WT, KVT, EPI_GATE, 2>(e, st, a, true)) return rc;
-    } else {  // Mlp::NoGating — :169
-      GemmArgs a = base_args(L.ff_in, xn, plain_map(M, d), M);
-      a.act = 1;
-      a.Y = ff; a.ymap = plain_map(M, w.hidden);
-      if (int rc = gemm_store<WT>(e, st, a)) return rc;
-    }
-    {
-      GemmArgs a = base_args(L.ff_out, ff, plain_map(M, w.hidden), M);
-      a.scale = L.ls2;
-      a.res = x; a.rmap = plain_map(M, d);
-      if (last && final_out) {
-        a.Y = final_out; a.ymap = final_map;
-      } else {
-        a.Y = x; a.ymap = plain_map(M, d);
-      }
-      if (!last) {  // the next layer's norm1
-        a.norm_w = w.layers[l + 1].n1w; a.norm_b = w.layers[l + 1].n1b; a.norm_out = xn; a.norm_eps = eps; a.norm_rms = c.norm;
-      } else if (post_norm_out) {  // e.g. LmModel::out_norm — core/lm.rs:1002
-        a.norm_w = post_norm_w; a.norm_b = nullptr; a.norm_out = post_norm_out; a.norm_eps = eps; a.norm_rms = c.norm;
-      }
-      if (int rc = gemm_store<WT>(e, st, a)) return rc;
-    }
+    if (int rc = transformer_layer_tail<WT, KVT>(e, st, w, l, act, B, T, final_out, final_map, post_norm_w, post_norm_out, ca)) return rc;
   }
   return 0;
 }
@@ -215,6 +228,39 @@ int join_groups(DsmDevice* e, hipStream_t st, size_t G) {
   return 0;
 }
 
+// SeaNetEncoder — core/seanet.rs:292-302 — over B items of r frames each (the per-frame geometries with T scaled by r): init conv,
+// per stage the residual block (ELU -> conv k3 -> ELU -> conv k1, + skip; :140-150) and the downsampling conv, then the final conv
+// into (out, omap).  The one chain of both paths: the step path runs it for B slots of one frame, the clip path once per clip of
+// r frames with cat_init pointing at that clip.  front_done: the caller's own kernel already ran the init conv and stage 0's
+// residual block (seanet_front_kernel).
+int seanet_encode(DsmDevice* e, hipStream_t st, const MimiW& w, SeanetEnc& s, const float* cat_init, int B, int r, float* out,
+                  RowMap omap, bool front_done = false) {
+  const RowMap none = plain_map(1, 1);
+  const size_t n = w.stages.size();
+  const ConvGeom g0 = over_frames(w.init_conv, r), gf = over_frames(w.final_conv, r);
+  if (!front_done)
+    if (int rc = run_conv(e, st, g0, cat_init, B, s.stages[0].y, plain_map(B * g0.T_out, g0.out_c), s.stages[0].cat_ra,
+                          cat_map(over_frames(w.stages[0].ra, r)), nullptr, none))
+      return rc;
+  for (size_t i = 0; i < n; ++i) {
+    const ConvGeom ra = over_frames(w.stages[i].ra, r), rb = over_frames(w.stages[i].rb, r), dn = over_frames(w.stages[i].down, r);
+    SeanetEnc::Stage& ss = s.stages[i];
+    if (!(i == 0 && front_done)) {
+      if (int rc = run_conv(e, st, ra, ss.cat_ra, B, nullptr, none, ss.cat_rb, cat_map(rb), nullptr, none)) return rc;
+      if (int rc = run_conv(e, st, rb, ss.cat_rb, B, nullptr, none, ss.cat_down, cat_map(dn), ss.y, plain_map(B * rb.T_out, rb.out_c)))
+        return rc;
+    }
+    if (i + 1 < n) {
+      if (int rc = run_conv(e, st, dn, ss.cat_down, B, s.stages[i + 1].y, plain_map(B * dn.T_out, dn.out_c), s.stages[i + 1].cat_ra,
+                            cat_map(over_frames(w.stages[i + 1].ra, r)), nullptr, none))
+        return rc;
+    } else if (int rc = run_conv(e, st, dn, ss.cat_down, B, nullptr, none, s.cat_final, cat_map(gf), nullptr, none)) {
+      return rc;
+    }
+  }
+  return run_conv(e, st, gf, s.cat_final, B, out, omap, nullptr, none, nullptr, none);
+}
+
 int mimi_encode_body(dsm_engine* e, int side, hipStream_t st);
 // Mimi::encode_step — core/mimi.rs:195-206.  PCM already sits in cat_init[:, S:, :], mask in s.mask.
 int mimi_encode(dsm_engine* e, int side, hipStream_t st) {
@@ -227,9 +273,8 @@ int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
   const RowMap none = plain_map(1, 1);
   e->tag_gemm[e->sid(st)] = DSM_PROF_GEMM_MIMI;
   e->tag_attn[e->sid(st)] = DSM_PROF_ATTN_MIMI;
-  // SeaNetEncoder::step — core/seanet.rs:292-302
   // The real Mimi front end (1 -> 64 k 7, residual block 64 -> 32 k 3 -> 64 k 1, f32, frames a multiple of 64) runs as one
-  // kernel whose intermediates stay in LDS (seanet_front_kernel); any other geometry takes the three GEMM launches.
+  // kernel whose intermediates stay in LDS (seanet_front_kernel); any other geometry takes seanet_encode's three GEMM launches.
   bool fused_front = false;
   {
     const MimiW::Stage& s0 = w.stages[0];
@@ -241,50 +286,24 @@ int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
                   s0.down.T_in == c.T_in && !c.replicate && !s0.ra.replicate;
     if (fused_front) {
       SeanetFrontArgs fa;
-      fa.cat_init = s.cat_init;
+      fa.cat_init = s.enc.cat_init;
       fa.w0 = reinterpret_cast<const float*>(c.lin.w); fa.b0 = c.lin.bias; fa.ld0 = c.lin.Kpad;
       fa.w1 = reinterpret_cast<const float*>(s0.ra.lin.w); fa.b1 = s0.ra.lin.bias; fa.ld1 = s0.ra.lin.Kpad;
       fa.w2 = reinterpret_cast<const float*>(s0.rb.lin.w); fa.b2 = s0.rb.lin.bias; fa.ld2 = s0.rb.lin.Kpad;
-      fa.cat_ra = s.stages[0].cat_ra;
-      fa.cat_down = s.stages[0].cat_down;
+      fa.cat_ra = s.enc.stages[0].cat_ra;
+      fa.cat_down = s.enc.stages[0].cat_down;
       fa.T = c.T_in; fa.S0 = c.S; fa.Sd = s0.down.S;
       const int ph = e->prof_begin(e->tag_gemm[e->sid(st)], st);
       hipLaunchKernelGGL(seanet_front_kernel<64>, dim3(c.T_in / 64, B), dim3(256), seanet_front_lds<64>(), st, fa);  // 32-frame tiles: same time (14.85 vs 14.79 ms of encode at B = 2048)
       e->prof_end(ph, st);
       HIPCHK(hipGetLastError());
-    } else if (int rc = run_conv(e, st, c, s.cat_init, B, s.stages[0].y, plain_map(B * c.T_out, c.out_c), s.stages[0].cat_ra,
-                                 cat_map(s0.ra), nullptr, none)) {
-      return rc;
-    }
-  }
-  for (size_t i = 0; i < w.stages.size(); ++i) {
-    const MimiW::Stage& sw = w.stages[i];
-    MimiState::Stage& ss = s.stages[i];
-    // SeaNetResnetBlock::step — core/seanet.rs:140-150: ELU -> conv k3 -> ELU -> conv k1, + skip
-    if (!(i == 0 && fused_front)) {
-      if (int rc = run_conv(e, st, sw.ra, ss.cat_ra, B, nullptr, none, ss.cat_rb, cat_map(sw.rb), nullptr, none)) return rc;
-      if (int rc = run_conv(e, st, sw.rb, ss.cat_rb, B, nullptr, none, ss.cat_down, cat_map(sw.down), ss.y,
-                            plain_map(B * sw.rb.T_out, sw.rb.out_c)))
-        return rc;
-    }
-    if (i + 1 < w.stages.size()) {
-      const MimiW::Stage& nx = w.stages[i + 1];
-      if (int rc = run_conv(e, st, sw.down, ss.cat_down, B, s.stages[i + 1].y,
-                            plain_map(B * sw.down.T_out, sw.down.out_c), s.stages[i + 1].cat_ra, cat_map(nx.ra), nullptr, none))
-        return rc;
-    } else {
-      if (int rc = run_conv(e, st, sw.down, ss.cat_down, B, nullptr, none, s.cat_final, cat_map(w.final_conv), nullptr, none))
-        return rc;
     }
   }
   const int Tt = w.final_conv.T_out, d = w.cfg.dimension;
-  if (int rc = run_conv(e, st, w.final_conv, s.cat_final, B, s.x_tr, plain_map(B * Tt, d), nullptr, none, nullptr, none))
-    return rc;
+  if (int rc = seanet_encode(e, st, w, s.enc, s.enc.cat_init, B, 1, s.act.x, plain_map(B * Tt, d), fused_front)) return rc;
   // ProjectedTransformer::step — core/batched_transformer.rs:584-602; its output lands in the downsample
   // conv's concat buffer
-  if (int rc = transformer_forward<float, float>(e, st, w.tr, s.tr, s.x_tr, s.xn, s.q, s.att, s.ff, B, Tt, s.mask,
-                                                  s.cat_ds, cat_map(w.downsample)))
-    return rc;
+  if (int rc = transformer_forward<float, float>(e, st, w.tr, s.tr, s.act, B, Tt, s.mask, s.cat_ds, cat_map(w.downsample))) return rc;
   if (s.first_call && w.downsample.S > 0) {  // replicate left pad on the module's first call
     hipLaunchKernelGGL(conv_replicate_init_kernel, dim3(B), dim3(256), 0, st, s.h_descs[s.ds_desc]);
     HIPCHK(hipGetLastError());
@@ -338,11 +357,7 @@ int alloc_dec_state(DsmDevice* e, const MimiW& w, MimiDecState& s, int B) {  // 
   if (int rc = e->dalloc(&s.q_rest, (size_t)B * c.quantizer_dim)) return rc;
   if (int rc = e->dalloc(&s.emb, (size_t)B * dim)) return rc;
   if (int rc = e->dalloc(&s.up_carry, (size_t)B * c.downsample_stride * dim)) return rc;
-  if (int rc = e->dalloc(&s.x_tr, (size_t)B * T2 * dim)) return rc;
-  if (int rc = e->dalloc(&s.xn, (size_t)B * T2 * dim)) return rc;
-  if (int rc = e->dalloc(&s.q, (size_t)B * T2 * dim)) return rc;
-  if (int rc = e->dalloc(&s.att, (size_t)B * T2 * dim)) return rc;
-  if (int rc = e->dalloc(&s.ff, (size_t)B * T2 * c.transformer.dim_feedforward)) return rc;
+  if (int rc = alloc_act(e, &s.act, (size_t)B * T2, dim, c.transformer.dim_feedforward)) return rc;  // (hidden, or more with gating)
   if (int rc = alloc_transformer_state(e, &s.tr, c.transformer, B, T2, false)) return rc;
   auto add = [&](float* cat, const ConvGeom& g) { add_desc(s.h_descs, cat, g); };  // (no decoder conv pads by replication)
   if (int rc = alloc_cat(e, &s.cat_init, w.dec_init, B)) return rc;
@@ -399,13 +414,11 @@ int mimi_decode_body(DsmDevice* e, const MimiW& w, MimiDecState& s, int B, hipSt
     }
   }
   // ConvTrUpsample1d::step — core/conv.rs:603-605
-  hipLaunchKernelGGL(upsample_dw_kernel, dim3(B), dim3(256), 0, st, s.emb, w.upsample_w, s.up_carry, s.x_tr, s.mask, dim,
+  hipLaunchKernelGGL(upsample_dw_kernel, dim3(B), dim3(256), 0, st, s.emb, w.upsample_w, s.up_carry, s.act.x, s.mask, dim,
                      c.downsample_stride, 2 * c.downsample_stride, s.first_call ? 0 : 1, s.started);
   HIPCHK(hipGetLastError());
   // decoder_transformer.step; its output lands in the decoder's first conv buffer
-  if (int rc = transformer_forward<float, float>(e, st, w.dec_tr, s.tr, s.x_tr, s.xn, s.q, s.att, s.ff, B, T2, s.mask,
-                                                  s.cat_init, cat_map(w.dec_init)))
-    return rc;
+  if (int rc = transformer_forward<float, float>(e, st, w.dec_tr, s.tr, s.act, B, T2, s.mask, s.cat_init, cat_map(w.dec_init))) return rc;
   // SeaNetDecoder::step — core/seanet.rs:452-467
   if (int rc = run_conv(e, st, w.dec_init, s.cat_init, B, nullptr, none, s.stages[0].x,
                         plain_map(B * T2, w.dec_init.out_c), nullptr, none))
@@ -469,8 +482,7 @@ int lm_group_body(dsm_engine* e, hipStream_t st, int g, uint32_t* d_text_out, fl
   const ActScratch sc = s.act.from_row(b0, d, w.tr.hidden);
   float* hidden = s.hidden + (size_t)b0 * d;
   int rc = with_kv_type(c.kv_bf16 != 0, [&](auto kv) {
-    return transformer_forward<uint16_t, decltype(kv)>(e, st, w.tr, grp.view, sc.x, sc.xn, sc.q, sc.att, sc.g, nb, 1, gmask, nullptr,
-                                                       plain_map(1, 1), w.out_norm, hidden, phase);
+    return transformer_forward<uint16_t, decltype(kv)>(e, st, w.tr, grp.view, sc, nb, 1, gmask, nullptr, plain_map(1, 1), w.out_norm, hidden, phase);
   });
   if (rc || phase == 1) return rc;  // hidden = out_norm(x) — core/lm.rs:1002 (fused behind the last layer's linear_out)
   float* logits = s.logits + (size_t)b0 * c.text_out_vocab_size;

@@ -9,17 +9,15 @@
 // Tolerance-pinned, not bit-pinned: the oracle has only the streaming Mimi (DESIGN.md, "Speaker encoder").  The attention sums in
 // its own fixed order; everything else uses the library's GEMMs and epilogues, whose sums do not depend on how many rows a launch has.
 //
+// Shared with the step path, each written once: the SEANet chain and its buffers (seanet_encode, alloc_seanet_enc — here one clip
+// of r frames per call where the step path has B slots of one frame) and every transformer layer from out_proj onward
+// (transformer_layer_tail).  This path's own: the normalisation of the clips, the RoPE table, the plain QKV store and
+// spk_attn_kernel in place of the ring front, and everything from ConvDownsample1d on.
+//
 // Nothing of the step or the decode side is touched: the scratch below is the clip path's own, the work runs on the model stream
 // between steps like dsm_tts_set_ca_src, and no graph slot is involved.
 
 namespace {
-
-ConvGeom spk_geom(const ConvGeom& g, int r) {  // the streaming geometry of one frame, over r frames
-  ConvGeom c = g;
-  c.T_in *= r;
-  c.T_out *= r;
-  return c;
-}
 
 int spk_frames_per_step(const MimiW& w) { return w.final_conv.T_out; }  // encoder-rate positions per 1920-sample frame
 
@@ -44,39 +42,17 @@ int spk_encode_body(dsm_tts* t, hipStream_t st, int c, int r) {
   e->tag_attn[e->sid(st)] = DSM_PROF_OTHER;
   // ---- SeaNetEncoder::forward, one clip at a time (layer 0 of a 10 s clip is 240 000 rows: a clip alone fills the chip, and the
   // scratch stays that of one clip whatever n_speakers is) ----
-  const ConvGeom g0 = spk_geom(w.init_conv, r), gf = spk_geom(w.final_conv, r);
+  const ConvGeom g0 = over_frames(w.init_conv, r);
   const long init_stride = (long)(g0.S + g0.T_in) * g0.in_c;
-  for (int i = 0; i < c; ++i) {
-    {
-      const ConvGeom ra0 = spk_geom(w.stages[0].ra, r);
-      if (int rc = run_conv(e, st, g0, s.cat_init + (long)i * init_stride, 1, s.stages[0].y, plain_map(g0.T_out, g0.out_c),
-                            s.stages[0].cat_ra, cat_map(ra0), nullptr, none))
-        return rc;
-    }
-    for (size_t k = 0; k < w.stages.size(); ++k) {
-      const ConvGeom ra = spk_geom(w.stages[k].ra, r), rb = spk_geom(w.stages[k].rb, r), dn = spk_geom(w.stages[k].down, r);
-      SpkEnc::Stage& ss = s.stages[k];
-      // SeaNetResnetBlock — core/seanet.rs:140-150: ELU -> conv k3 -> ELU -> conv k1, + skip
-      if (int rc = run_conv(e, st, ra, ss.cat_ra, 1, nullptr, none, ss.cat_rb, cat_map(rb), nullptr, none)) return rc;
-      if (int rc = run_conv(e, st, rb, ss.cat_rb, 1, nullptr, none, ss.cat_down, cat_map(dn), ss.y, plain_map(rb.T_out, rb.out_c)))
-        return rc;
-      if (k + 1 < w.stages.size()) {
-        const ConvGeom nra = spk_geom(w.stages[k + 1].ra, r);
-        if (int rc = run_conv(e, st, dn, ss.cat_down, 1, s.stages[k + 1].y, plain_map(dn.T_out, dn.out_c), s.stages[k + 1].cat_ra,
-                              cat_map(nra), nullptr, none))
-          return rc;
-      } else if (int rc = run_conv(e, st, dn, ss.cat_down, 1, nullptr, none, s.cat_final, cat_map(gf), nullptr, none)) {
-        return rc;
-      }
-    }
-    if (int rc = run_conv(e, st, gf, s.cat_final, 1, s.x + (long)i * T * d, plain_map(T, d), nullptr, none, nullptr, none)) return rc;
-  }
-  // ---- ProjectedTransformer::forward over all clips' positions: the layer loop of transformer_forward at M = c * T rows, the
-  // QKV projection a plain store (no ring, no builder), its output into the downsample convolution's concat buffer ----
-  const ConvGeom gd = spk_geom(w.downsample, r);
+  for (int i = 0; i < c; ++i)
+    if (int rc = seanet_encode(e, st, w, s.enc, s.enc.cat_init + (long)i * init_stride, 1, r, s.act.x + (long)i * T * d, plain_map(T, d)))
+      return rc;
+  // ---- ProjectedTransformer::forward over all clips' positions, M = c * T rows: the QKV projection a plain store (no ring, no
+  // builder) and causal attention within each clip, then the layer tail of the step path; the last layer's output lands in the
+  // downsample convolution's concat buffer ----
+  const ConvGeom gd = over_frames(w.downsample, r);
   if (gd.S > 0 && !gd.replicate)  // a zero left pad: where it sits depends on the clip length of this call
     HIPCHK(hipMemsetAsync(s.cat_ds, 0, sizeof(float) * (size_t)c * (gd.S + gd.T_in) * gd.in_c, st));
-  const float eps = tc.norm == 1 ? 1e-8f : 1e-5f;
   const float* rope = tc.positional_embedding == 1 ? s.rope_cs : nullptr;  // null: q and k are not rotated
   if (rope) {
     const int n = T * (hd / 2);
@@ -84,57 +60,19 @@ int spk_encode_body(dsm_tts* t, hipStream_t st, int c, int r) {
                        w.tr.rope_pos_before ? 0 : spk_frames_per_step(w));
     HIPCHK(hipGetLastError());
   }
-  if (int rc = run_norm(e, st, s.xn, s.x, w.tr.layers[0].n1w, w.tr.layers[0].n1b, M, d, tc.norm)) return rc;
+  if (int rc = run_norm(e, st, s.act.xn, s.act.x, w.tr.layers[0].n1w, w.tr.layers[0].n1b, M, d, tc.norm)) return rc;
   for (int l = 0; l < tc.num_layers; ++l) {
-    const TLayerW& L = w.tr.layers[l];
-    const bool last = l == tc.num_layers - 1;
-    {
-      GemmArgs a = base_args(L.in_proj, s.xn, plain_map(M, d), M);
-      a.Y = s.qkv; a.ymap = plain_map(M, 3 * d);
-      if (int rc = gemm_store<float>(e, st, a)) return rc;
-    }
-    if (int rc = hd == 32 ? spk_launch_attn<32>(e, st, s.att, s.qkv, rope, T, H, c)
-                          : spk_launch_attn<64>(e, st, s.att, s.qkv, rope, T, H, c))
+    GemmArgs a = base_args(w.tr.layers[l].in_proj, s.act.xn, plain_map(M, d), M);
+    a.Y = s.qkv; a.ymap = plain_map(M, 3 * d);
+    if (int rc = gemm_store<float>(e, st, a)) return rc;
+    if (int rc = hd == 32 ? spk_launch_attn<32>(e, st, s.act.att, s.qkv, rope, T, H, c)
+                          : spk_launch_attn<64>(e, st, s.act.att, s.qkv, rope, T, H, c))
       return rc;
-    {
-      GemmArgs a = base_args(L.out_proj, s.att, plain_map(M, d), M);
-      a.scale = L.ls1;
-      a.res = s.x; a.rmap = plain_map(M, d);
-      a.Y = s.x; a.ymap = plain_map(M, d);
-      a.norm_w = L.n2w; a.norm_b = L.n2b; a.norm_out = s.xn; a.norm_eps = eps; a.norm_rms = tc.norm;
-      if (int rc = gemm_store<float>(e, st, a)) return rc;
-    }
-    if (tc.gating) {
-      GemmArgs a = base_args(L.ff_in, s.xn, plain_map(M, d), M);
-      a.N = w.tr.hidden;
-      a.nt_stride = w.tr.hidden;
-      a.Y = s.ff; a.ymap = plain_map(M, w.tr.hidden);
-      if (int rc = launch_gemm_t<float, float, EPI_GATE, 2>(e, st, a, true)) return rc;
-    } else {
-      GemmArgs a = base_args(L.ff_in, s.xn, plain_map(M, d), M);
-      a.act = 1;
-      a.Y = s.ff; a.ymap = plain_map(M, w.tr.hidden);
-      if (int rc = gemm_store<float>(e, st, a)) return rc;
-    }
-    {
-      GemmArgs a = base_args(L.ff_out, s.ff, plain_map(M, w.tr.hidden), M);
-      a.scale = L.ls2;
-      a.res = s.x; a.rmap = plain_map(M, d);
-      if (last) {
-        a.Y = s.cat_ds; a.ymap = cat_map(gd);
-      } else {
-        a.Y = s.x; a.ymap = plain_map(M, d);
-        a.norm_w = w.tr.layers[l + 1].n1w; a.norm_b = w.tr.layers[l + 1].n1b; a.norm_out = s.xn; a.norm_eps = eps; a.norm_rms = tc.norm;
-      }
-      if (int rc = gemm_store<float>(e, st, a)) return rc;
-    }
+    if (int rc = transformer_layer_tail<float, float>(e, st, w.tr, l, s.act, c, T, s.cat_ds, cat_map(gd), nullptr, nullptr, nullptr)) return rc;
   }
   // ---- ConvDownsample1d::forward — core/conv.rs:527-547: the left pad of a clip repeats its first frame ----
   if (gd.S > 0) {
-    ConvStateDesc dsc;
-    dsc.cat = s.cat_ds; dsc.bstride = (long)(gd.S + gd.T_in) * gd.in_c; dsc.S = gd.S; dsc.T = gd.T_in; dsc.C = gd.in_c;
-    dsc.replicate = gd.replicate ? 1 : 0;
-    if (gd.replicate) hipLaunchKernelGGL(conv_replicate_init_kernel, dim3(c), dim3(256), 0, st, dsc);
+    if (gd.replicate) hipLaunchKernelGGL(conv_replicate_init_kernel, dim3(c), dim3(256), 0, st, conv_desc(s.cat_ds, gd));
     HIPCHK(hipGetLastError());
   }
   if (int rc = run_conv(e, st, gd, s.cat_ds, c, s.latent, plain_map(c * r, d), nullptr, none, nullptr, none)) return rc;
@@ -209,11 +147,11 @@ int spk_debug_read(dsm_tts* t, const char* name, float* out, size_t cap) {
   }
   const int c = s.last_c, r = s.last_r;
   if (!strcmp(name, "spk.pcm_norm")) {  // [c][clip_len]: the clips behind the first convolution's left pad
-    const ConvGeom g0 = spk_geom(w.init_conv, r);
+    const ConvGeom g0 = over_frames(w.init_conv, r);
     const size_t len = (size_t)g0.T_in * g0.in_c, stride = (size_t)(g0.S + g0.T_in) * g0.in_c;
     size_t n = 0;
     for (int i = 0; i < c && n + len <= cap; ++i, n += len)
-      HIPCHK(hipMemcpy(out + n, s.cat_init + (size_t)i * stride + (size_t)g0.S * g0.in_c, sizeof(float) * len, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(out + n, s.enc.cat_init + (size_t)i * stride + (size_t)g0.S * g0.in_c, sizeof(float) * len, hipMemcpyDeviceToHost));
     return (int)n;
   }
   if (!strcmp(name, "spk.latent")) {  // [c * r][dimension]: encode_pre_quantize, transposed
@@ -274,9 +212,9 @@ int spk_attach_impl(dsm_tts* t, int n_speakers, const char* lm_path) {
   }
   dsm_st_close(f);
   if (rc) return rc;
-  size_t bytes = 0;
+  size_t floats = 0;
   auto alloc = [&](float** p, size_t count) {
-    bytes += count * sizeof(float);
+    floats += count;
     return e->dalloc(p, count);
   };
   if ((rc = pack_linear(e, &s.proj, wp.data(), cond, d, false, nullptr))) return rc;
@@ -288,25 +226,17 @@ int spk_attach_impl(dsm_tts* t, int n_speakers, const char* lm_path) {
     if ((rc = e->upload(&s.pos, pos.data(), pos.size()))) return rc;
   }
   // scratch of the longest clip (max_r frames): one clip through the convolutions, n_speakers through the transformer
-  const ConvGeom g0 = spk_geom(w.init_conv, max_r), gf = spk_geom(w.final_conv, max_r), gd = spk_geom(w.downsample, max_r);
+  const ConvGeom g0 = over_frames(w.init_conv, max_r), gd = over_frames(w.downsample, max_r);
   const size_t len = (size_t)g0.T_in * g0.in_c, T = (size_t)fps * max_r, rows = (size_t)n_speakers * T;
   if ((rc = alloc(&s.pcm, (size_t)n_speakers * len))) return rc;
   if ((rc = alloc(&s.stdev, (size_t)n_speakers))) return rc;
-  if ((rc = alloc(&s.cat_init, (size_t)n_speakers * (g0.S + g0.T_in) * g0.in_c))) return rc;
-  s.stages.resize(w.stages.size());
-  for (size_t k = 0; k < w.stages.size(); ++k) {
-    const ConvGeom ra = spk_geom(w.stages[k].ra, max_r), rb = spk_geom(w.stages[k].rb, max_r), dn = spk_geom(w.stages[k].down, max_r);
-    if ((rc = alloc(&s.stages[k].y, (size_t)ra.T_in * ra.in_c))) return rc;
-    if ((rc = alloc(&s.stages[k].cat_ra, (size_t)(ra.S + ra.T_in) * ra.in_c))) return rc;
-    if ((rc = alloc(&s.stages[k].cat_rb, (size_t)(rb.S + rb.T_in) * rb.in_c))) return rc;
-    if ((rc = alloc(&s.stages[k].cat_down, (size_t)(dn.S + dn.T_in) * dn.in_c))) return rc;
-  }
-  if ((rc = alloc(&s.cat_final, (size_t)(gf.S + gf.T_in) * gf.in_c))) return rc;
-  if ((rc = alloc(&s.x, rows * d))) return rc;
-  if ((rc = alloc(&s.xn, rows * d))) return rc;
+  if ((rc = alloc_seanet_enc(e, &s.enc, w, n_speakers, 1, max_r, nullptr, &floats))) return rc;
+  // not alloc_act: its q would be a [rows][d] buffer this path never touches, on top of qkv
+  if ((rc = alloc(&s.act.x, rows * d))) return rc;
+  if ((rc = alloc(&s.act.xn, rows * d))) return rc;
   if ((rc = alloc(&s.qkv, rows * 3 * d))) return rc;
-  if ((rc = alloc(&s.att, rows * d))) return rc;
-  if ((rc = alloc(&s.ff, rows * (size_t)w.tr.hidden))) return rc;
+  if ((rc = alloc(&s.act.att, rows * d))) return rc;
+  if ((rc = alloc(&s.act.g, rows * (size_t)w.tr.hidden))) return rc;
   if ((rc = alloc(&s.rope_cs, T * hd))) return rc;
   if ((rc = alloc(&s.cat_ds, (size_t)n_speakers * (gd.S + gd.T_in) * gd.in_c))) return rc;
   if ((rc = alloc(&s.latent, (size_t)n_speakers * max_r * d))) return rc;
@@ -315,7 +245,7 @@ int spk_attach_impl(dsm_tts* t, int n_speakers, const char* lm_path) {
   if ((rc = e->halloc(&s.h_rows, (size_t)s.pos_rows * cond))) return rc;
   if ((rc = e->new_event(&s.ev_a, hipEventDefault))) return rc;
   if ((rc = e->new_event(&s.ev_b, hipEventDefault))) return rc;
-  s.scratch_bytes = bytes;
+  s.scratch_bytes = floats * sizeof(float);
   s.n_speakers = n_speakers;
   s.cond_dim = cond;
   s.max_r = max_r;
@@ -371,13 +301,13 @@ int dsm_tts_encode_voice(dsm_tts* t, const float* pcm, int n_clips, int clip_len
   ApiShared api(e);
   hipStream_t st = e->s_model;
   HIPCHK(hipStreamSynchronize(st));
-  const ConvGeom g0 = spk_geom(t->mimi_w.init_conv, r);
+  const ConvGeom g0 = over_frames(t->mimi_w.init_conv, r);
   const long stride = (long)(g0.S + g0.T_in) * g0.in_c;
   HIPCHK(hipEventRecord(s.ev_a, st));
   HIPCHK(hipMemcpyAsync(s.pcm, pcm, sizeof(float) * (size_t)c * clip_len, hipMemcpyHostToDevice, st));
   // the clips' zero left pads: where they sit depends on the clip length of this call
-  HIPCHK(hipMemsetAsync(s.cat_init, 0, sizeof(float) * (size_t)c * stride, st));
-  hipLaunchKernelGGL(spk_normalize_kernel, dim3(c), dim3(1024), 0, st, s.pcm, clip_len, s.cat_init + (long)g0.S * g0.in_c, stride, s.stdev);
+  HIPCHK(hipMemsetAsync(s.enc.cat_init, 0, sizeof(float) * (size_t)c * stride, st));
+  hipLaunchKernelGGL(spk_normalize_kernel, dim3(c), dim3(1024), 0, st, s.pcm, clip_len, s.enc.cat_init + (long)g0.S * g0.in_c, stride, s.stdev);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(s.h_stdev, s.stdev, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

@@ -27,13 +27,10 @@ struct SpkEnc {
   int pos_rows = 0;  // rows of the position table
   Linear proj;       // output_proj [cond_dim][dimension] f32
   float *pad = nullptr, *pos = nullptr;  // learnt_padding [cond_dim], pos_emb [pos_rows][cond_dim]
-  float *pcm = nullptr, *stdev = nullptr, *cat_init = nullptr;  // [n_speakers][clip], [n_speakers], [n_speakers][S0 + clip]
-  struct Stage {
-    float *y = nullptr, *cat_ra = nullptr, *cat_rb = nullptr, *cat_down = nullptr;  // one clip
-  };
-  std::vector<Stage> stages;
-  float* cat_final = nullptr;  // one clip
-  float *x = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *ff = nullptr, *rope_cs = nullptr;  // [n_speakers * T] rows
+  float *pcm = nullptr, *stdev = nullptr;  // [n_speakers][clip], [n_speakers]
+  SeanetEnc enc;                           // cat_init [n_speakers][S0 + clip]; everything behind it holds one clip
+  ActScratch act;                          // [n_speakers * T] rows; q is not used (no ring): the projection lands in qkv
+  float *qkv = nullptr, *rope_cs = nullptr;  // [n_speakers * T][3 d], [T][head_dim]
   float *cat_ds = nullptr, *latent = nullptr, *rows = nullptr;
   float *h_stdev = nullptr, *h_rows = nullptr;  // pinned
   hipEvent_t ev_a = nullptr, ev_b = nullptr;    // device time of the last encode
@@ -438,7 +435,7 @@ int tts_depformer(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp) {
     h.pos = grp.dtr.pos; h.idx = grp.dtr.idx; h.active = t->d_rrun + r0;
     h.start_pos = grp.dtr.start_pos; h.widx = grp.dtr.widx;
     h.ctx = dc.context; h.nw = tw.layers[0].n1w; h.nb = tw.layers[0].n1b;
-    h.eps = dc.norm == 1 ? 1e-8f : 1e-5f; h.rms = dc.norm;
+    h.eps = norm_eps(dc.norm); h.rms = dc.norm;
     return h;
   };
   for (int k = 0; k < S; ++k) {
@@ -448,8 +445,8 @@ int tts_depformer(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp) {
       hipLaunchKernelGGL(dep_head_kernel, dim3(B), dim3(256), 0, st, head_args(0), t->d_last + b0);
       HIPCHK(hipGetLastError());
     }
-    if (int rc = transformer_forward<uint16_t, float>(e, st, tw, grp.dtr, da.x, da.xn, da.q, da.att, da.g, B, 1, t->d_rrun + r0,
-                                                      nullptr, plain_map(1, 1), nullptr, nullptr, 0, nullptr, /*head_done=*/true))
+    if (int rc = transformer_forward<uint16_t, float>(e, st, tw, grp.dtr, da, B, 1, t->d_rrun + r0, nullptr, plain_map(1, 1), nullptr,
+                                                      nullptr, 0, nullptr, /*head_done=*/true))
       return rc;
     LogitSrc src{};
     {
@@ -497,8 +494,8 @@ int tts_group_body(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp, bool run_dep) 
                      t->d_tokens + (size_t)r0 * (1 + nc), nc, d, c.audio_vocab_size);
   HIPCHK(hipGetLastError());
   int rc = with_kv_type(c.kv_bf16 != 0, [&](auto kv) {  // forward_cond, or forward_ca for rows that carry a source (core/lm.rs:957-1067)
-    return transformer_forward<uint16_t, decltype(kv)>(e, st, t->lm.tr, grp.tr, sc.x, sc.xn, sc.q, sc.att, sc.g, B, 1, t->d_rmask + r0, nullptr,
-                                                       plain_map(1, 1), t->lm.out_norm, hidden, 0, ca);
+    return transformer_forward<uint16_t, decltype(kv)>(e, st, t->lm.tr, grp.tr, sc, B, 1, t->d_rmask + r0, nullptr, plain_map(1, 1),
+                                                       t->lm.out_norm, hidden, 0, ca);
   });
   if (rc) return rc;
   {
