@@ -119,7 +119,7 @@ ABI_SYMBOLS = [
     "dsm_asr_create", "dsm_asr_create_from_arena", "dsm_asr_weight_arena", "dsm_destroy", "dsm_last_error", "dsm_mimi_encode_step", "dsm_asr_step_tokens",
     "dsm_asr_step_pcm", "dsm_asr_poll_msgs", "dsm_asr_reset_slot", "dsm_mimi_reset_slot", "dsm_sync",
     "dsm_get_metrics", "dsm_batch_size", "dsm_n_q", "dsm_mimi_encode_step_dev", "dsm_asr_step_tokens_dev",
-    "dsm_streams_join", "dsm_debug_read", "dsm_asr_step_pcm_dev", "dsm_prof_enable", "dsm_prof_read",
+    "dsm_streams_join", "dsm_debug_read", "dsm_debug_gemm_plan", "dsm_asr_step_pcm_dev", "dsm_prof_enable", "dsm_prof_read",
     "dsm_asr_create_replica", "dsm_asr_set_seed", "dsm_debug_set_positions", "dsm_debug_set_text_tokens", "dsm_mimi_decode_step", "dsm_mimi_decode_step_dev",
     "dsm_lm_stream_groups", "dsm_debug_serialize_groups", "dsm_prof_read_device", "dsm_prof_timeline", "dsm_prof_timeline_read",
     "dsm_wav_decode", "dsm_mp3_decode", "dsm_mp3_decode_info", "dsm_mp3_probe", "dsm_resample", "dsm_pcm_decode",
@@ -203,6 +203,8 @@ def load_library(path=None):
     lib.dsm_lm_stream_groups.restype = C.c_int
     lib.dsm_debug_serialize_groups.argtypes = [vp, C.c_int]
     lib.dsm_debug_serialize_groups.restype = C.c_int
+    lib.dsm_debug_gemm_plan.argtypes = [C.c_int] * 9 + [C.c_char_p, C.c_size_t]
+    lib.dsm_debug_gemm_plan.restype = C.c_int
     lib.dsm_wav_decode.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t),
                                    C.POINTER(C.c_int)]
     lib.dsm_wav_decode.restype = C.c_int

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/dsm.h"
+#include "dsm_gemm_plan.h"
 
 #define HIPCHK_E(eng, expr)                                                                         \
   do {                                                                                              \
@@ -49,10 +50,11 @@ struct DsmDevice {
   // default: with the fused kernel in the encoder stream, an encode that overlaps the LM's dot_mode 1 kernels on the same CUs
   // emits codes that differ from run to run; the three launches are bit-reproducible and cost ~2 % per step
   bool fuse_front = false;
-  int chunk_loop_min_tiles = 384;  // DSM_CHUNK_LOOP_MIN: whole-K workgroups from this many (n, m) tiles on (swept at B = 512 / 1024: 384 best)
-  int loop_depth = 4;           // DSM_LOOP_DEPTH=2: two-block rolling window (fewer registers, three waves per SIMD) where four is the default
-  int smallk_min_tiles = 1024;  // DSM_SMALLK_MIN: one-chunk GEMMs (K <= 256) move to gemm_loop_kernel from this many 64-row tiles on
-  int smallk_mt = 4;            // DSM_SMALLK_MT: 16-row tiles per workgroup of those launches
+  // the GEMM plan's knobs (GemmKnobs, dsm_gemm_plan.h, which holds their defaults and what they mean)
+  int chunk_loop_min_tiles = GemmKnobs().chunk_loop_min_tiles;  // DSM_CHUNK_LOOP_MIN
+  int loop_depth = GemmKnobs().loop_depth;                      // DSM_LOOP_DEPTH
+  int smallk_min_tiles = GemmKnobs().smallk_min_tiles;          // DSM_SMALLK_MIN
+  int smallk_mt = GemmKnobs().smallk_mt;                        // DSM_SMALLK_MT
   // ---- fixed per engine and dot_mode (dsm_read_env) ----
   size_t attn_lds_pad = 60000;  // extra dynamic LDS per attention workgroup of a large launch (2 per CU; 40000 = 3 per CU)
   int dot_mode = 0;             // the engine configuration's dot_mode: 1 = the bf16-weight GEMMs in "bx3" (gemm_bx3_kernel)

@@ -24,6 +24,7 @@
 #include "../../include/dsm.h"
 #include "dsm_device.h"
 #include "dsm_config_presets.h"
+#include "dsm_gemm_plan.h"
 #include "dsm_kernels.h"
 #include "dsm_numerics.h"
 #include "dsm_safetensors.h"
@@ -38,21 +39,18 @@ static int dsm_env_int(const char* name, int dflt) {
   return v ? atoi(v) : dflt;
 }
 static void dsm_read_env(DsmDevice* e, bool stt) {
-  // dot_mode 1, STT engine only: the bx3 loop is cheaper per tile, so whole-K workgroups pay from 192 (n, m) tiles on (r03 sweep,
-  // profiles/r03/experiments/chunk_loop_min_mode1.txt: B = 400 13.2 -> 12.0 ms, B = 1024 27.9 -> 26.7), and the bf16 GEMMs leave
-  // the vector ALU to the attention waves, so large attention launches run three workgroups per CU (r03: 52.1 -> 50.4 ms at
-  // B = 2048, 59.8 -> 56.9 at 2304; four: 53.7).  The TTS engine has always kept 384 and 60000 in both modes (it never ran
-  // these two lines); the difference is kept on purpose: dropping it would change which kernels a TTS step launches.
-  if (stt && e->dot_mode == 1) {
-    e->chunk_loop_min_tiles = 192;
-    e->attn_lds_pad = 40000;
-  }
+  // dot_mode 1, STT engine only: whole-K workgroups pay from 192 (n, m) tiles on (gemm_default_knobs, dsm_gemm_plan.h), and the
+  // bf16 GEMMs leave the vector ALU to the attention waves, so large attention launches run three workgroups per CU (r03: 52.1 ->
+  // 50.4 ms at B = 2048, 59.8 -> 56.9 at 2304; four: 53.7).  The TTS engine has always kept 384 and 60000 in both modes; the
+  // difference is kept on purpose: dropping it would change which kernels a TTS step launches.
+  e->chunk_loop_min_tiles = gemm_default_knobs(stt, e->dot_mode).chunk_loop_min_tiles;
+  if (stt && e->dot_mode == 1) e->attn_lds_pad = 40000;
   e->use_graphs = dsm_env_int("DSM_GRAPHS", 1) != 0;
   e->fuse_qkv = dsm_env_int("DSM_FUSE_QKV", 1) != 0;
   e->stream_prio = dsm_env_int("DSM_STREAM_PRIO", 0) != 0;  // the TTS engine's two streams have no priorities: ignored there
   e->fuse_front = dsm_env_int("DSM_FUSE_FRONT", 0) != 0;
   e->chunk_loop_min_tiles = dsm_env_int("DSM_CHUNK_LOOP_MIN", e->chunk_loop_min_tiles);
-  e->loop_depth = dsm_env_int("DSM_LOOP_DEPTH", 4) == 2 ? 2 : 4;
+  e->loop_depth = dsm_env_int("DSM_LOOP_DEPTH", e->loop_depth) == 2 ? 2 : 4;
   e->smallk_min_tiles = dsm_env_int("DSM_SMALLK_MIN", e->smallk_min_tiles);
   const int mt = dsm_env_int("DSM_SMALLK_MT", e->smallk_mt);
   if (mt == 1 || mt == 2 || mt == 4) e->smallk_mt = mt;
@@ -822,81 +820,94 @@ int alloc_mimi_state(DsmDevice* e, MimiState* s, const MimiW& w, int B) {
 // ----------------------------------------------------------------------------------------------
 // GEMM launch
 // ----------------------------------------------------------------------------------------------
-// whole-K-in-the-workgroup GEMMs (dsm_gemm_wk.h): dot_mode 1, bf16 weights, at most four K-chunks, M <= 64
-bool wk_applicable(const DsmDevice* e, bool bf16_weights, int Kpad, int K, int M) {
-  const int chunks = (Kpad + DSM_KC - 1) / DSM_KC;
-  return bf16_weights && e->dot_mode == 1 && K % 32 == 0 && Kpad == K && chunks <= 4 && M <= 64;
-}
+// What launch_gemm hands back when it left the split-K slabs to the caller's next kernel: chunk c of row m starts at
+// ws + c * cstride + m * ld.  ws is null when the product was reduced (or never split).
+struct Slabs {
+  const float* ws = nullptr;
+  long ld = 0, cstride = 0;
+  int chunks = 0;
+};
 
-// The one launch of launch_gemm_tiled, for MT 16-row tiles per workgroup.
-//   dot_mode 1, bf16 weights (bx3): whole K in the workgroup -> gemm_bx3_kernel<.., true>; split-K at M <= 32 -> gemm_bx3u_kernel,
-//     which issues every load of its chunk up front (r04; 48 KB of LDS at MT = 2, 24 KB at MT = 1); split-K at MT = 4 ->
-//     gemm_bx3_kernel<.., false>
-//   otherwise: whole K (roll) -> gemm_loop_kernel with a four- or two-block load window; split-K -> gemm_tile_kernel
+// The main launch of a plan, for MT 16-row tiles per workgroup.  Every kernel form is instantiated for every MT it exists at;
+// which one runs is the plan's (dsm_gemm_plan.h).
 template <typename WT, typename KVT, int EPI, int NT, int MT>
-void launch_tile(hipStream_t st, dim3 grid, const GemmArgs& a, bool bx3, bool roll, bool deep) {
-  constexpr int DMAX = LoopDepth<WT, NT>::MAX;
-  if (bx3 && EPI != EPI_RVQ) {
-    if (a.chunk_loop > 1) hipLaunchKernelGGL((gemm_bx3_kernel<KVT, MT, NT, EPI, true>), grid, dim3(256), 0, st, a);
-    else if constexpr (MT == 4) hipLaunchKernelGGL((gemm_bx3_kernel<KVT, 4, NT, EPI, false>), grid, dim3(256), 0, st, a);
-    else if constexpr (MT == 2) hipLaunchKernelGGL((gemm_bx3u_kernel<KVT, 2, NT, EPI, 8, 0, 4>), grid, dim3(256), 8 * 3 * 32 * 32 * 2, st, a);
-    else hipLaunchKernelGGL((gemm_bx3u_kernel<KVT, 1, NT, EPI, 8>), grid, dim3(256), 8 * 3 * 16 * 32 * 2, st, a);
-  } else if (roll && deep) hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MT, NT, EPI, DMAX>), grid, dim3(256), 0, st, a);
-  else if (roll) hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MT, NT, EPI, 2>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((gemm_tile_kernel<WT, KVT, MT, NT, EPI>), grid, dim3(256), 0, st, a);
+void launch_form(const GemmPlan& p, hipStream_t st, const GemmArgs& a) {
+  const dim3 grid(p.gx, p.gy, p.gz), block(p.block);
+  switch (p.form) {
+    case GEMM_MFMA:
+      if (p.k_aligned) hipLaunchKernelGGL((gemm_mfma_kernel<WT, KVT, MT, NT, EPI, true>), grid, block, p.lds, st, a);
+      else hipLaunchKernelGGL((gemm_mfma_kernel<WT, KVT, MT, NT, EPI, false>), grid, block, p.lds, st, a);
+      break;
+    case GEMM_MFMA_BX3:
+      if (p.k_aligned) hipLaunchKernelGGL((gemm_mfma_kernel<WT, KVT, MT, NT, EPI, true, true>), grid, block, p.lds, st, a);
+      else hipLaunchKernelGGL((gemm_mfma_kernel<WT, KVT, MT, NT, EPI, false, true>), grid, block, p.lds, st, a);
+      break;
+    case GEMM_TILE: hipLaunchKernelGGL((gemm_tile_kernel<WT, KVT, MT, NT, EPI>), grid, block, p.lds, st, a); break;
+    case GEMM_LOOP2: hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MT, NT, EPI, 2>), grid, block, p.lds, st, a); break;
+    case GEMM_LOOP_DEEP: hipLaunchKernelGGL((gemm_loop_kernel<WT, KVT, MT, NT, EPI, LoopDepth<WT, NT>::MAX>), grid, block, p.lds, st, a); break;
+    case GEMM_BX3_LOOP: hipLaunchKernelGGL((gemm_bx3_kernel<KVT, MT, NT, EPI, true>), grid, block, p.lds, st, a); break;
+    case GEMM_BX3_LOOP_NT2:
+      if constexpr (MT == 4)
+        hipLaunchKernelGGL((gemm_bx3_kernel<KVT, 4, (NT == 1 ? 2 : NT), (EPI == EPI_GATE ? EPI_STORE : EPI), true>), grid, block, p.lds, st, a);
+      break;
+    case GEMM_BX3_SPLIT:
+      if constexpr (MT == 4) hipLaunchKernelGGL((gemm_bx3_kernel<KVT, 4, NT, EPI, false>), grid, block, p.lds, st, a);
+      break;
+    case GEMM_BX3U_2:
+      if constexpr (MT == 2) hipLaunchKernelGGL((gemm_bx3u_kernel<KVT, 2, NT, EPI, 8, 0, 4>), grid, block, p.lds, st, a);
+      break;
+    case GEMM_BX3U_1:
+      if constexpr (MT == 1) hipLaunchKernelGGL((gemm_bx3u_kernel<KVT, 1, NT, EPI, 8>), grid, block, p.lds, st, a);
+      break;
+    case GEMM_WK:
+      if constexpr (MT == 1 && EPI == EPI_GATE && NT == 2)
+        hipLaunchKernelGGL((gemm_wk_kernel<KVT, 1, 2, EPI_GATE, 1, 4, 2, true, 4>), grid, block, p.lds, st, a);
+      break;
+    case GEMM_NO_FIT: break;
+  }
 }
 
+// Y (and / or Y2, the row norm behind it) = epilogue(X W^T): fills a GemmQuery from the arguments, asks plan_gemm
+// (dsm_gemm_plan.h) and executes the plan — the workspace, the main launch, the reduce, the row norm.  It decides nothing itself
+// and does not write the caller's arguments.  slabs: non-null when the caller's next kernel can sum split-K slabs itself; its ws
+// is non-null on return exactly when they were left to it.
 template <typename WT, typename KVT, int EPI, int NT>
-int launch_gemm_tiled(DsmDevice* e, hipStream_t st, GemmArgs& a) {
-  int chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
-  const int gx = (a.N + 63) / 64;
-  const bool bx3 = e->dot_mode == 1 && sizeof(WT) == 2;  // dot_mode 1: every bf16-weight GEMM on the bf16 matrix pipe
+int launch_gemm(DsmDevice* e, hipStream_t st, const GemmArgs& args, bool aligned, Slabs* slabs = nullptr) {
+  static_assert(EPI_STORE == GEMM_EPI_STORE && EPI_QKV == GEMM_EPI_QKV && EPI_GATE == GEMM_EPI_GATE && EPI_RVQ == GEMM_EPI_RVQ, "");
+  static_assert(LoopDepth<uint16_t, 1>::MAX == 4 && LoopDepth<uint16_t, 2>::MAX == 2 && LoopDepth<float, 1>::MAX == 2, "plan_gemm's `deep`");
   auto ok4 = [](const RowMap& m) { return m.ld % 4 == 0 && m.bstride % 4 == 0; };
-  a.vec = (a.N % 4 == 0) && (!a.Y || ok4(a.ymap)) && (!a.Y2 || ok4(a.y2map)) && (!a.res || ok4(a.rmap));
-  // ---- chunk loop.  Enough (n, m) tiles to fill the chip (large batches; the Mimi convs, whose M is B x frames): no
-  // split-K across workgroups — each walks the chunks itself and sums them in order in registers, so the slabs
-  // (chunks x M x N floats written, then read back by a reduce launch) disappear.
-  a.chunk_loop = 0;
-  if (chunks > 1 && (long)gx * ((a.M + 63) / 64) >= e->chunk_loop_min_tiles) {
-    a.chunk_loop = chunks;
-    a.defer_reduce = 0;
-    chunks = 1;
+  GemmQuery q;
+  q.weight_bf16 = sizeof(WT) == 2;
+  q.epi = EPI;
+  q.NT = NT;
+  q.M = args.M; q.N = args.N; q.K = args.K; q.Kpad = args.Kpad;
+  q.nt_stride = args.nt_stride;
+  q.aligned = aligned;
+  q.has_Y = args.Y != nullptr; q.has_Y2 = args.Y2 != nullptr; q.has_res = args.res != nullptr;
+  q.has_bias = args.bias != nullptr; q.has_norm = args.norm_out != nullptr;
+  q.y_ok4 = ok4(args.ymap); q.y2_ok4 = ok4(args.y2map); q.res_ok4 = ok4(args.rmap);
+  q.y_bstride0 = args.ymap.bstride == 0;
+  q.may_defer = slabs != nullptr;
+  GemmKnobs k;
+  k.dot_mode = e->dot_mode;
+  k.chunk_loop_min_tiles = e->chunk_loop_min_tiles;
+  k.smallk_min_tiles = e->smallk_min_tiles;
+  k.smallk_mt = e->smallk_mt;
+  k.loop_depth = e->loop_depth;
+  const GemmPlan p = plan_gemm(q, k);
+  if (p.form == GEMM_NO_FIT) {
+    e->set_error("GEMM K=%d: chunk partials do not fit in LDS", args.K);
+    return DSM_ERR_INVALID;
   }
-  // ---- whole-K gate.  r04: short reductions (the DepFormer's: K = 1024) keep the whole K inside the workgroup — four waves, one
-  // chunk each, 16 rows x one (gate, up) tile pair per workgroup, the epilogue behind the ordered LDS sum: no slabs, no reduce
-  // launch.  experiments/gemm_wk_probe: gate 7.5 us against 13.4 (10.9 with gemm_bx3u_kernel) at M = 32; at K = 2048 the
-  // activation re-read (every workgroup reads 16 x K x 4 bytes from L2) makes it lose (27 against 20 us).
-  if constexpr (EPI == EPI_GATE && NT == 2) {
-    if (wk_applicable(e, sizeof(WT) == 2, a.Kpad, a.K, a.M) && chunks > 1 && a.N % 16 == 0) {
-      a.ts = e->timeline ? e->dev_ts_slot(e->tag_gemm[e->sid(st)], e->sid(st), 1, 2) : nullptr;
-      const int ph = e->prof_begin(e->tag_gemm[e->sid(st)], st);
-      hipLaunchKernelGGL((gemm_wk_kernel<KVT, 1, 2, EPI_GATE, 1, 4, 2, true, 4>), dim3(a.N / 16, 1, (a.M + 15) / 16), dim3(256),
-                         (size_t)chunks * 2 * 1024, st, a);
-      e->prof_end(ph, st);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-  }
-  // ---- MT: 16-row tiles per workgroup
-  int MT = a.M > 32 ? 4 : (a.M > 16 ? 2 : 1);
-  while (MT > 1 && (long)gx * chunks * ((a.M + 16 * MT - 1) / (16 * MT)) < 256) MT /= 2;  // cover the 256 CUs
-  // 33..64 rows, dot_mode 1, a launch of at most 256 workgroups (out_proj of a 2048-wide model): two 32-row z-tiles on
-  // gemm_bx3u_kernel instead of one 64-row tile on gemm_bx3_kernel — 12.8 against 15.4 us with its reduce (experiments/gemm_wk_probe 3,
-  // form 5); the wider launches (QKV, gate, ff_out) tie or lose that way and keep MT = 4.
-  if (MT == 4 && bx3 && chunks > 1 && a.M <= 64 && (long)gx * chunks <= 256 && EPI == EPI_STORE) MT = 2;
-  // one K-chunk and thousands of m-tiles (the first SEANet layers at large batches: K = 32..192, M = B x 1920): a
-  // workgroup is one short dependent chain — loads, one to six MFMA blocks, residual load, store — so what counts is how
-  // many of them a CU holds; gemm_tile_kernel's up-front window of eight blocks costs 200-230 VGPRs (two workgroups per CU),
-  // gemm_loop_kernel's two-block window 150 (three).  Mimi encode alone at B = 2048: 17.7 -> 16.6 ms; 8-row tiles no better.
-  const bool smallk = chunks == 1 && a.chunk_loop == 0 && (long)gx * ((a.M + 63) / 64) >= e->smallk_min_tiles && !bx3;
-  if (smallk && e->smallk_mt < MT) MT = e->smallk_mt;
-  // ---- split-K workspace
-  a.ws_ntiles = (((NT - 1) * a.nt_stride) >> 4) + gx * 4;
-  const int mtiles = (a.M + 15) / 16;
-  if (chunks > 1) {
-    const int wsid = e->sid(st);
-    size_t need = (size_t)chunks * mtiles * a.ws_ntiles * 256 * sizeof(float);
-    if (need > e->gemm_ws_cap[wsid]) {  // first use of a bigger shape: grow (never happens in steady state)
+  GemmArgs a = args;
+  a.vec = p.vec;
+  a.chunk_loop = p.chunk_loop;
+  a.wg_cols = p.wg_cols;
+  a.nt_stride = p.nt_stride;
+  a.ws_ntiles = p.ws_ntiles;
+  const int sid = e->sid(st);
+  if (p.ws_bytes) {
+    if (p.ws_bytes > e->gemm_ws_cap[sid]) {  // first use of a bigger shape: grow (never happens in steady state)
       if (e->capturing) {  // a graph capture cannot allocate: give up on this capture, the caller reruns the body eagerly
         e->capture_failed = true;
         e->set_error("split-K workspace grew during a graph capture");
@@ -904,104 +915,49 @@ int launch_gemm_tiled(DsmDevice* e, hipStream_t st, GemmArgs& a) {
       }
       e->ws_gen += 1;
       HIPCHK(hipStreamSynchronize(st));
-      if (e->gemm_ws[wsid]) HIPCHK(hipFree(e->gemm_ws[wsid]));
-      e->gemm_ws[wsid] = nullptr;
-      e->gemm_ws_cap[wsid] = 0;
-      void* p = nullptr;
-      HIPCHK(hipMalloc(&p, need));
-      e->gemm_ws[wsid] = reinterpret_cast<float*>(p);
-      e->gemm_ws_cap[wsid] = need;
+      if (e->gemm_ws[sid]) HIPCHK(hipFree(e->gemm_ws[sid]));
+      e->gemm_ws[sid] = nullptr;
+      e->gemm_ws_cap[sid] = 0;
+      void* ws = nullptr;
+      HIPCHK(hipMalloc(&ws, p.ws_bytes));
+      e->gemm_ws[sid] = reinterpret_cast<float*>(ws);
+      e->gemm_ws_cap[sid] = p.ws_bytes;
     }
-    a.ws = e->gemm_ws[wsid];
+    a.ws = e->gemm_ws[sid];
   }
-  // ---- the launch
-  dim3 grid(gx, chunks, (a.M + 16 * MT - 1) / (16 * MT));
-  // dot_mode 1, whole-K form, plain epilogues, from 256 workgroups on: two n-tiles per wave (128 weight rows per workgroup).  With
-  // one n-tile a wave reads 12 LDS fragments (12 KB) per block for 12 MFMAs and the LDS, not the matrix pipe, bounds the loop; the
-  // gate has always run two.
-  const bool nt2 = NT == 1 && bx3 && a.chunk_loop > 1 && MT == 4 && (EPI == EPI_STORE || EPI == EPI_QKV) && a.N % 128 == 0 &&
-                   (long)(a.N / 128) * grid.z >= 256;
-  if (nt2) {
-    grid.x = a.N / 128;
-    a.wg_cols = 128;
-    a.nt_stride = 64;
+  if (p.tiled) a.ts = e->timeline ? e->dev_ts_slot(e->tag_gemm[sid], sid, 1, 2) : nullptr;
+  const int ph = e->prof_begin(e->tag_gemm[sid], st);
+  switch (p.MT) {
+    case 4: launch_form<WT, KVT, EPI, NT, 4>(p, st, a); break;
+    case 2: launch_form<WT, KVT, EPI, NT, 2>(p, st, a); break;
+    default: launch_form<WT, KVT, EPI, NT, 1>(p, st, a); break;
   }
-  a.ts = e->timeline ? e->dev_ts_slot(e->tag_gemm[e->sid(st)], e->sid(st), 1, 2) : nullptr;
-  const int ph = e->prof_begin(e->tag_gemm[e->sid(st)], st);
-  const bool roll = a.chunk_loop > 1 || smallk;  // whole K in the workgroup with a rolling load window
-  const bool deep = LoopDepth<WT, NT>::MAX == 4 && e->loop_depth == 4 && !smallk;
-  if (nt2) hipLaunchKernelGGL((gemm_bx3_kernel<KVT, 4, (NT == 1 ? 2 : NT), (EPI == EPI_GATE ? EPI_STORE : EPI), true>), grid, dim3(256), 0, st, a);
-  else if (MT == 4) launch_tile<WT, KVT, EPI, NT, 4>(st, grid, a, bx3, roll, deep);
-  else if (MT == 2) launch_tile<WT, KVT, EPI, NT, 2>(st, grid, a, bx3, roll, deep);
-  else launch_tile<WT, KVT, EPI, NT, 1>(st, grid, a, bx3, roll, deep);
-  // ---- the reduce
-  const bool rows_ok = (EPI == EPI_STORE) && a.norm_out && a.vec && !a.Y2 && a.Y && a.N <= 4096 && a.ymap.bstride == 0;
-  if (chunks > 1 && !((EPI == EPI_QKV || EPI == EPI_STORE) && a.defer_reduce)) {  // deferred: the consumer sums the slabs (AttnFused, LogitSrc)
-    if (rows_ok) {
-      if (a.N <= 1024) hipLaunchKernelGGL(gemm_reduce_rows_kernel<1>, dim3(a.M), dim3(256), 0, st, a, chunks);
-      else if (a.N <= 2048) hipLaunchKernelGGL(gemm_reduce_rows_kernel<2>, dim3(a.M), dim3(512), 0, st, a, chunks);
-      else hipLaunchKernelGGL(gemm_reduce_rows_kernel<4>, dim3(a.M), dim3(1024), 0, st, a, chunks);
-    } else {
-      const int out_tiles = mtiles * ((a.N + 15) / 16);
-      hipLaunchKernelGGL((gemm_reduce_kernel<KVT, EPI>), dim3((out_tiles + 3) / 4), dim3(256), 0, st, a, chunks);
+  switch (p.reduce) {
+    case GEMM_RED_NONE: case GEMM_RED_CONSUMER: break;
+    case GEMM_RED_ROWS1: hipLaunchKernelGGL(gemm_reduce_rows_kernel<1>, dim3(a.M), dim3(256), 0, st, a, p.chunks); break;
+    case GEMM_RED_ROWS2: hipLaunchKernelGGL(gemm_reduce_rows_kernel<2>, dim3(a.M), dim3(512), 0, st, a, p.chunks); break;
+    case GEMM_RED_ROWS4: hipLaunchKernelGGL(gemm_reduce_rows_kernel<4>, dim3(a.M), dim3(1024), 0, st, a, p.chunks); break;
+    case GEMM_RED_TILES: {
+      const int out_tiles = ((a.M + 15) / 16) * ((a.N + 15) / 16);
+      hipLaunchKernelGGL((gemm_reduce_kernel<KVT, EPI>), dim3((out_tiles + 3) / 4), dim3(256), 0, st, a, p.chunks);
+      break;
     }
   }
   e->prof_end(ph, st);
   HIPCHK(hipGetLastError());
-  if (a.norm_out && !(chunks > 1 && rows_ok)) {  // the norm could not be fused: run it on the stored rows
+  if (p.row_norm) {
     hipLaunchKernelGGL(row_norm_kernel, dim3(a.M), dim3(256), 0, st, a.norm_out, a.Y, a.norm_w, a.norm_b, a.M,
                        a.N, a.norm_eps, a.norm_rms);
     HIPCHK(hipGetLastError());
   }
-  return 0;
-}
-
-template <typename WT, typename KVT, int EPI, int NT>
-int launch_gemm_t(DsmDevice* e, hipStream_t st, GemmArgs& a, bool aligned) {
-  if (aligned && a.K % 32 == 0) return launch_gemm_tiled<WT, KVT, EPI, NT>(e, st, a);
-  const int chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
-  const int rounds = (chunks + 15) / 16;          // chunks per wave when there are more than 16
-  const int S = (chunks + rounds - 1) / rounds;   // waves per workgroup
-  const int tiles16 = (a.N + 15) / 16;  // for the gate a.N is the hidden width: one (gate, up) tile pair per block
-  const int nx = (EPI == EPI_GATE) ? tiles16 : (tiles16 + NT - 1) / NT;
-  // M-tiles per wave: as many as possible (weights are re-read once per m-group) while the grid still covers
-  // the 256 CUs at least twice and the chunk partials fit in LDS
-  int MT = (NT == 2) ? 2 : 4;  // NT=2 x MT=4 would need > 128 VGPRs (spills under the 1024-thread cap)
-  while (MT > 1 && (a.M <= 16 * (MT / 2) || (long)nx * ((a.M + 16 * MT - 1) / (16 * MT)) * S < 2048 ||
-                    (chunks > 1 && (size_t)chunks * NT * MT * 1024 > 64 * 1024)))
-    MT /= 2;
-  if (chunks > 1 && (size_t)chunks * NT * MT * 1024 > 160 * 1024) {
-    e->set_error("GEMM K=%d: chunk partials do not fit in LDS", a.K);
-    return DSM_ERR_INVALID;
-  }
-  // 16-byte epilogue accesses need every row offset to be a multiple of 4 floats
-  auto ok4 = [](const RowMap& m) { return m.ld % 4 == 0 && m.bstride % 4 == 0; };
-  a.vec = (a.N % 4 == 0) && (!a.Y || ok4(a.ymap)) && (!a.Y2 || ok4(a.y2map)) && (!a.res || ok4(a.rmap));
-  aligned = aligned && (a.K % 32 == 0);  // the fast kernel has no K-tail handling
-  dim3 grid(nx, (a.M + 16 * MT - 1) / (16 * MT));
-  dim3 block(64 * S);
-  size_t lds = chunks > 1 ? (size_t)chunks * NT * MT * 1024 : 0;
-  const bool bx3 = e->dot_mode == 1 && sizeof(WT) == 2 && EPI != EPI_RVQ;
-#define DSM_LAUNCH(MTv, AL)                                                                                   \
-  do {                                                                                                        \
-    if (bx3) hipLaunchKernelGGL((gemm_mfma_kernel<WT, KVT, MTv, NT, EPI, AL, true>), grid, block, lds, st, a); \
-    else hipLaunchKernelGGL((gemm_mfma_kernel<WT, KVT, MTv, NT, EPI, AL>), grid, block, lds, st, a);          \
-  } while (0)
-  const int ph = e->prof_begin(e->tag_gemm[e->sid(st)], st);
-  if (MT == 1) {
-    if (aligned) DSM_LAUNCH(1, true); else DSM_LAUNCH(1, false);
-  } else if (MT == 2) {
-    if (aligned) DSM_LAUNCH(2, true); else DSM_LAUNCH(2, false);
-  } else {
-    if (aligned) DSM_LAUNCH(4, true); else DSM_LAUNCH(4, false);
-  }
-  e->prof_end(ph, st);
-#undef DSM_LAUNCH
-  HIPCHK(hipGetLastError());
-  if (a.norm_out) {
-    hipLaunchKernelGGL(row_norm_kernel, dim3(a.M), dim3(256), 0, st, a.norm_out, a.Y, a.norm_w, a.norm_b, a.M,
-                       a.N, a.norm_eps, a.norm_rms);
-    HIPCHK(hipGetLastError());
+  if (slabs) {
+    *slabs = Slabs{};
+    if (p.reduce == GEMM_RED_CONSUMER) {
+      slabs->ws = a.ws;
+      slabs->ld = (long)p.ws_ntiles * 16;
+      slabs->cstride = (long)((a.M + 15) / 16) * 16 * slabs->ld;
+      slabs->chunks = p.chunks;
+    }
   }
   return 0;
 }
@@ -1105,9 +1061,20 @@ GemmArgs base_args(const Linear& L, const float* X, RowMap xmap, int M) {
   return a;
 }
 
+float norm_eps(int rms) { return rms ? 1e-8f : 1e-5f; }  // LayerNorm / RmsNorm — core/batched_transformer.rs:236-252
+
+// the row norm behind this GEMM: out = norm(Y), fused into the split-K reduce where the plan can (gemm_reduce_rows_kernel)
+void set_norm(GemmArgs& a, const float* w, const float* b, float* out, int rms) {
+  a.norm_w = w;
+  a.norm_b = b;
+  a.norm_out = out;
+  a.norm_eps = norm_eps(rms);
+  a.norm_rms = rms;
+}
+
 template <typename WT>
-int gemm_store(DsmDevice* e, hipStream_t st, GemmArgs& a, bool aligned = true) {
-  return launch_gemm_t<WT, float, EPI_STORE, 1>(e, st, a, aligned);
+int gemm_store(DsmDevice* e, hipStream_t st, const GemmArgs& a, bool aligned = true, Slabs* slabs = nullptr) {
+  return launch_gemm<WT, float, EPI_STORE, 1>(e, st, a, aligned, slabs);
 }
 
 // conv as a GEMM over the consumer's concat buffer; output goes to Y (raw) and/or Y2 (ELU copy, usually the

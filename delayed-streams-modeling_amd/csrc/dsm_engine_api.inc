@@ -53,8 +53,6 @@ int launch_attn(DsmDevice* e, hipStream_t st, float* out, const float* q, const 
   return DSM_ERR_INVALID;
 }
 
-float norm_eps(int rms) { return rms ? 1e-8f : 1e-5f; }  // LayerNorm / RmsNorm — core/batched_transformer.rs:236-252
-
 int run_norm(DsmDevice* e, hipStream_t st, float* y, const float* x, const float* w, const float* b, int rows, int d,
              int rms) {
   hipLaunchKernelGGL(row_norm_kernel, dim3(rows), dim3(256), 0, st, y, x, w, b, rows, d, norm_eps(rms), rms);
@@ -73,7 +71,6 @@ int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, 
                            float* final_out, RowMap final_map, const float* post_norm_w, float* post_norm_out, const CaState* ca) {
   const dsm_transformer_config& c = w.cfg;
   const int d = c.d_model, H = c.num_heads, hd = d / H, M = B * T;
-  const float eps = norm_eps(c.norm);
   const TLayerW& L = w.layers[l];
   const bool last = (l == c.num_layers - 1);
   {
@@ -81,11 +78,8 @@ int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, 
     a.scale = L.ls1;
     a.res = act.x; a.rmap = plain_map(M, d);
     a.Y = act.x; a.ymap = plain_map(M, d);
-    if (ca) {  // norm_cross follows instead of norm2 — core/transformer.rs:755-757
-      a.norm_w = L.ncw; a.norm_b = L.ncb; a.norm_out = act.xn; a.norm_eps = norm_eps(w.ca_norm_rms); a.norm_rms = w.ca_norm_rms;
-    } else {
-      a.norm_w = L.n2w; a.norm_b = L.n2b; a.norm_out = act.xn; a.norm_eps = eps; a.norm_rms = c.norm;  // norm2
-    }
+    if (ca) set_norm(a, L.ncw, L.ncb, act.xn, w.ca_norm_rms);  // norm_cross follows instead of norm2 — core/transformer.rs:755-757
+    else set_norm(a, L.n2w, L.n2b, act.xn, c.norm);            // norm2
     if (int rc = gemm_store<WT>(e, st, a)) return rc;
   }
   if (ca) {  // xs = residual + cross_attn.forward(norm_cross(xs), ca_src) — core/transformer.rs:753-760, :320-352
@@ -94,14 +88,11 @@ int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, 
     {
       GemmArgs a = base_args(L.ca_q, act.xn, plain_map(M, d), M);  // in_proj_q, (b, t, H, hd)
       a.Y = act.q; a.ymap = plain_map(M, d);
-      // T = 1, split-K, plain epilogue: the ordered slab sum of the query runs in the attention kernel's prologue (r04)
-      a.defer_reduce = (T == 1 && a.Kpad > DSM_KC && a.K % 32 == 0 && !a.bias && d % 4 == 0 && e->fuse_qkv) ? 1 : 0;
-      if (int rc = gemm_store<WT>(e, st, a)) return rc;
-      if (a.defer_reduce) {  // (cleared by the launcher when a workgroup walked the whole K itself)
-        none.ws = a.ws;
-        none.ld = (long)a.ws_ntiles * 16;
-        none.cstride = (long)((M + 15) / 16) * 16 * none.ld;
-        none.chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
+      // T = 1 and slabs left by the plan: the ordered slab sum of the query runs in the attention kernel's prologue (r04)
+      Slabs sl;
+      if (int rc = gemm_store<WT>(e, st, a, true, T == 1 && e->fuse_qkv ? &sl : nullptr)) return rc;
+      if (sl.ws) {
+        none.ws = sl.ws; none.ld = sl.ld; none.cstride = sl.cstride; none.chunks = sl.chunks;
         none.q_only = 1;
       }
     }
@@ -111,7 +102,7 @@ int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, 
     GemmArgs a = base_args(L.ca_out, ca->att, plain_map(M, d), M);  // out_proj; gating = Normal
     a.res = act.x; a.rmap = plain_map(M, d);
     a.Y = act.x; a.ymap = plain_map(M, d);
-    a.norm_w = L.n2w; a.norm_b = L.n2b; a.norm_out = act.xn; a.norm_eps = eps; a.norm_rms = c.norm;  // norm2
+    set_norm(a, L.n2w, L.n2b, act.xn, c.norm);  // norm2
     if (int rc = gemm_store<WT>(e, st, a)) return rc;
   }
   if (c.gating) {  // Mlp::Gating — core/batched_transformer.rs:170-176
@@ -119,7 +110,7 @@ int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, 
     a.N = w.hidden;
     a.nt_stride = w.hidden;
     a.Y = act.g; a.ymap = plain_map(M, w.hidden);
-    if (int rc = launch_gemm_t<WT, KVT, EPI_GATE, 2>(e, st, a, true)) return rc;
+    if (int rc = launch_gemm<WT, KVT, EPI_GATE, 2>(e, st, a, true)) return rc;
   } else {  // Mlp::NoGating — :169
     GemmArgs a = base_args(L.ff_in, act.xn, plain_map(M, d), M);
     a.act = 1;
@@ -134,11 +125,8 @@ int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, 
   } else {
     a.Y = act.x; a.ymap = plain_map(M, d);
   }
-  if (!last) {  // the next layer's norm1
-    a.norm_w = w.layers[l + 1].n1w; a.norm_b = w.layers[l + 1].n1b; a.norm_out = act.xn; a.norm_eps = eps; a.norm_rms = c.norm;
-  } else if (post_norm_out) {  // e.g. LmModel::out_norm — core/lm.rs:1002
-    a.norm_w = post_norm_w; a.norm_b = nullptr; a.norm_out = post_norm_out; a.norm_eps = eps; a.norm_rms = c.norm;
-  }
+  if (!last) set_norm(a, w.layers[l + 1].n1w, w.layers[l + 1].n1b, act.xn, c.norm);  // the next layer's norm1
+  else if (post_norm_out) set_norm(a, post_norm_w, nullptr, post_norm_out, c.norm);    // e.g. LmModel::out_norm — core/lm.rs:1002
   return gemm_store<WT>(e, st, a);
 }
 
@@ -178,15 +166,11 @@ int transformer_forward(DsmDevice* e, hipStream_t st, const TransformerW& w, Tra
       a.widx = s.widx;
       a.rope_cs = c.positional_embedding == 1 ? s.rope_cs : nullptr;
       a.active = d_mask;
-      // T = 1 with a split-K QKV GEMM: its ordered reduce + RoPE + ring scatter run in the attention kernel's prologue
-      a.defer_reduce = (T == 1 && L.in_proj.Kpad > DSM_KC && L.in_proj.K % 32 == 0 && e->fuse_qkv) ? 1 : 0;
-      if (int rc = launch_gemm_t<WT, KVT, EPI_QKV, 1>(e, st, a, true)) return rc;
-      if (a.defer_reduce) {
-        const int mtiles = (M + 15) / 16;
-        fq.ws = a.ws;
-        fq.ld = (long)a.ws_ntiles * 16;
-        fq.cstride = (long)mtiles * 16 * fq.ld;
-        fq.chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;  // (launch_gemm_tiled clears defer_reduce when it walks the chunks in-workgroup)
+      // T = 1 and slabs left by the plan: the ordered reduce + RoPE + ring scatter run in the attention kernel's prologue
+      Slabs sl;
+      if (int rc = launch_gemm<WT, KVT, EPI_QKV, 1>(e, st, a, true, T == 1 && e->fuse_qkv ? &sl : nullptr)) return rc;
+      if (sl.ws) {
+        fq.ws = sl.ws; fq.ld = sl.ld; fq.cstride = sl.cstride; fq.chunks = sl.chunks;
         fq.rope_cs = a.rope_cs;
         fq.widx = s.widx;
       }
@@ -326,7 +310,7 @@ int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
       const Linear& cb = r.codebooks[i];
       GemmArgs a = base_args(cb, res, plain_map(B, qd), B);
       a.pval = s.pval; a.pidx = s.pidx;
-      if (int rc = launch_gemm_t<float, float, EPI_RVQ, 1>(e, st, a, true)) return rc;
+      if (int rc = launch_gemm<float, float, EPI_RVQ, 1>(e, st, a, true)) return rc;
       hipLaunchKernelGGL(rvq_select_kernel, dim3(B), dim3(256), 0, st, s.pval, s.pidx, (cb.N + 15) / 16, B, s.codes, n_q,
                          which == 0 ? 0 : 1 + i, res, reinterpret_cast<const float*>(cb.w), qd, cb.Kpad);
       HIPCHK(hipGetLastError());
@@ -1570,6 +1554,24 @@ int dsm_debug_read(dsm_engine* e, const char* name, float* out, size_t cap) {
   if (n > cap) n = cap;
   HIPCHK(hipMemcpy(out, src, sizeof(float) * n, hipMemcpyDeviceToHost));
   return (int)n;
+}
+
+int dsm_debug_gemm_plan(int stt, int dot_mode, int weight_bf16, int epi, int nt, int M, int N, int K, int flags, char* buf, size_t cap) {
+  if (epi < EPI_STORE || epi > EPI_RVQ || (nt != 1 && nt != 2) || M < 1 || N < 1 || K < 1 || !buf || !cap) return DSM_ERR_INVALID;
+  GemmQuery q;
+  q.weight_bf16 = weight_bf16 != 0;
+  q.epi = epi;
+  q.NT = nt;
+  q.M = M; q.N = N; q.K = K;
+  q.Kpad = round_up(K, 32);                // pack_linear
+  q.nt_stride = epi == EPI_GATE ? N : 16;  // base_args; the gate's up rows sit `hidden` below its gate rows
+  q.aligned = flags & DSM_GEMMQ_ALIGNED;
+  q.has_Y = flags & DSM_GEMMQ_Y; q.has_Y2 = flags & DSM_GEMMQ_Y2; q.has_res = flags & DSM_GEMMQ_RES;
+  q.has_bias = flags & DSM_GEMMQ_BIAS; q.has_norm = flags & DSM_GEMMQ_NORM;
+  q.y_ok4 = flags & DSM_GEMMQ_Y_OK4; q.y2_ok4 = flags & DSM_GEMMQ_Y2_OK4; q.res_ok4 = flags & DSM_GEMMQ_RES_OK4;
+  q.y_bstride0 = flags & DSM_GEMMQ_Y_PLAIN;
+  q.may_defer = flags & DSM_GEMMQ_MAY_DEFER;
+  return gemm_plan_line(plan_gemm(q, gemm_default_knobs(stt != 0, dot_mode)), q.has_norm, buf, cap);
 }
 
 }  // extern "C"

@@ -452,14 +452,11 @@ int tts_depformer(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp) {
     {
       GemmArgs a = base_args(t->dep.out[k], da.x, plain_map(B, D), B);
       a.Y = dlogits; a.ymap = plain_map(B, V);
-      // a split-K product with a plain epilogue: leave the slabs to the sampler launch (one launch less per slice)
-      a.defer_reduce = (a.Kpad > DSM_KC && a.K % 32 == 0 && !a.bias && V % 4 == 0) ? 1 : 0;
-      if (int rc = gemm_store<uint16_t>(e, st, a)) return rc;
-      if (a.defer_reduce) {  // (cleared by the launcher when a workgroup walked the whole K itself)
-        src.ws = a.ws;
-        src.ld = (long)a.ws_ntiles * 16;
-        src.cstride = (long)((B + 15) / 16) * 16 * src.ld;
-        src.chunks = (a.Kpad + DSM_KC - 1) / DSM_KC;
+      // slabs left by the plan go to the sampler launch (one launch less per slice)
+      Slabs sl;
+      if (int rc = gemm_store<uint16_t>(e, st, a, true, &sl)) return rc;
+      if (sl.ws) {
+        src.ws = sl.ws; src.ld = sl.ld; src.cstride = sl.cstride; src.chunks = sl.chunks;
         src.store = dlogits;
       } else {
         src.rows = dlogits;

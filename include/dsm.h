@@ -444,6 +444,29 @@ int dsm_debug_set_text_tokens(dsm_engine*, const uint32_t* tokens);
  * Returns the number of floats written, or <0. */
 int dsm_debug_read(dsm_engine*, const char* name, float* out, size_t cap);
 
+/* Diagnostic, no device needed: which kernel a matrix product gets.  Runs the GEMM launcher's decision (plan_gemm,
+ * csrc/dsm_gemm_plan.h) for an engine kind (stt: the STT engine's defaults, else the TTS engine's) and dot_mode with no DSM_*
+ * variable set, for a weight of [N][K] (bf16 or f32), an epilogue (0 store, 1 QKV, 2 gate with N = the hidden width, 3 RVQ),
+ * nt n-tiles per wave (2 for the gate, else 1) and M activation rows, and writes one line to buf, e.g.
+ *   "bx3u<2> grid=32x4x2 wg=256 lds=49152 chunks=4 loop=0 reduce=rows2 norm=fused mt=2 ... ws=1048576"
+ * (kernel form<16-row tiles per workgroup>, grid, workgroup size, dynamic LDS bytes, K-chunks across workgroups, K-chunks
+ * walked inside one, the reduce launch: none / consumer / rows1|2|4 / tiles, the row norm: none / fused / separate, then the
+ * launcher-owned GemmArgs fields and the split-K workspace bytes).  flags: DSM_GEMMQ_* below.  Returns the line's length, or <0. */
+enum {
+  DSM_GEMMQ_ALIGNED = 1 << 0,   /* every activation row starts on a multiple of 4 floats */
+  DSM_GEMMQ_Y = 1 << 1,         /* an output Y, a second (ELU) output Y2, a residual, a bias, a row norm behind the product */
+  DSM_GEMMQ_Y2 = 1 << 2,
+  DSM_GEMMQ_RES = 1 << 3,
+  DSM_GEMMQ_BIAS = 1 << 4,
+  DSM_GEMMQ_NORM = 1 << 5,
+  DSM_GEMMQ_Y_OK4 = 1 << 6,     /* the row strides of Y / Y2 / the residual are multiples of 4 floats */
+  DSM_GEMMQ_Y2_OK4 = 1 << 7,
+  DSM_GEMMQ_RES_OK4 = 1 << 8,
+  DSM_GEMMQ_Y_PLAIN = 1 << 9,   /* Y is one plain [M][ld] matrix (no per-batch stride) */
+  DSM_GEMMQ_MAY_DEFER = 1 << 10 /* the caller's next kernel can sum split-K slabs itself */
+};
+int dsm_debug_gemm_plan(int stt, int dot_mode, int weight_bf16, int epi, int nt, int M, int N, int K, int flags, char* buf, size_t cap);
+
 /* ------------------------------------------------------------------------------------------------
  * Audio ingest helpers (host only; SURVEY.md §8(f) rank 3, first part).
  * dsm_wav_decode: channel 0 of a RIFF/WAVE body as f32 — what srv/utils.rs:263-305 `pcm_decode` hands the worker
