@@ -994,11 +994,13 @@ __global__ __launch_bounds__(256 * ITS) void gemm_reduce_rows_kernel(GemmArgs a,
   const long ld = (long)a.ws_ntiles * 16, cstride = (long)((a.M + 15) >> 4) * 16 * ld;
   const int i = it * 1024 + 4 * t;
   const bool live = i < d;
-  const float* p = a.ws + (long)m * ld + (live ? i : 4 * t);  // a group beyond d re-reads the row's first group and is dropped
+  // A thread beyond d re-reads the row's first four elements and is dropped.  (Not 4 * t: with d < 1024 that is past the row for
+  // t >= d / 4, and past the workspace, the residual and the norm weights for the last row — Mimi's d = 512.)
+  const int ic = live ? i : 0;
+  const float* p = a.ws + (long)m * ld + ic;
   // The epilogue's operands — bias, LayerScale, residual, norm weights — do not depend on the sums: requested FIRST, unconditionally
   // (an absent operand re-reads the slab word, a valid address, and is never used), so that they travel with the slab loads instead
   // of costing two more dependent memory round trips behind them (r04: 5.6 -> 4.x us per launch, 64 launches per step on the chain).
-  const int ic = live ? i : 4 * t;
   const f32x4 bias4 = *reinterpret_cast<const f32x4*>(a.bias ? a.bias + ic : p);
   const f32x4 scale4 = *reinterpret_cast<const f32x4*>(a.scale ? a.scale + ic : p);
   const f32x4 res4 = *reinterpret_cast<const f32x4*>(a.res ? a.res + a.rmap.off(m) + ic : p);

@@ -2,7 +2,8 @@
 """Writes tests/golden/gemm_plans.json: matrix-product queries and the line dsm_debug_gemm_plan answers for each (no GPU needed).
 (a) one query per branch of plan_gemm (csrc/dsm_gemm_plan.h) at the smallest shape that reaches it, (b) the products of the
 shipped presets, shapes and row maps worked out from the configurations the way the engines' call sites do.  Run it after a
-deliberate change of a gate and read the diff: every changed line is a shape that moved to another kernel or launch shape."""
+deliberate change of a gate and read the diff: every changed line is a shape that moved to another kernel or launch shape.
+Importable: mimi_products(mimi, B, stt, dot_mode) returns the rows of one Mimi at any batch (tests/decoder_plans.py uses it)."""
 import ctypes as C
 import json
 import os
@@ -16,49 +17,51 @@ STORE, QKV, GATE, RVQ = 0, 1, 2, 3
 ALIGNED, Y, Y2, RES, BIAS, NORM, Y_OK4, Y2_OK4, RES_OK4, Y_PLAIN, MAY_DEFER = (1 << i for i in range(11))
 OK = Y_OK4 | Y2_OK4 | RES_OK4          # unset row maps of base_args are all zero: ld % 4 == 0 holds
 BASE = ALIGNED | OK | Y_PLAIN          # a linear on plain [M][ld] matrices
-rows = []
 
 
-def add(name, stt, dot_mode, bf16, epi, nt, M, N, K, flags):
+def add(rows, name, stt, dot_mode, bf16, epi, nt, M, N, K, flags):
     rows.append(dict(name=name, stt=stt, dot_mode=dot_mode, weight_bf16=bf16, epi=epi, nt=nt, M=M, N=N, K=K, flags=flags))
 
 
-# ---- (a) one row per branch ----
-add("generic: K % 32 != 0", 1, 0, 0, STORE, 1, 16, 64, 100, BASE | Y)
-add("one chunk f32: tile kernel, fused epilogue, separate row norm", 1, 0, 0, STORE, 1, 16, 64, 256, BASE | Y | NORM)
-add("two chunks mode 0: slabs left to the consumer", 1, 0, 1, STORE, 1, 16, 1024, 512, BASE | Y | MAY_DEFER)
-add("two chunks mode 0: reduce rows<1> with the norm, N = 1024", 1, 0, 1, STORE, 1, 16, 1024, 512, BASE | Y | RES | NORM)
-add("two chunks mode 0: reduce rows<2> with the norm, N = 2048", 1, 0, 1, STORE, 1, 16, 2048, 512, BASE | Y | RES | NORM)
-add("two chunks mode 0: reduce rows<4> with the norm, N = 4096", 1, 0, 1, STORE, 1, 16, 4096, 512, BASE | Y | RES | NORM)
-add("two chunks mode 0: tile reduce, no norm", 1, 0, 1, STORE, 1, 16, 1024, 512, BASE | Y)
-add("chunk loop at 384 tiles", 1, 0, 1, STORE, 1, 384 * 64, 64, 512, BASE | Y)
-add("no chunk loop at 383 tiles", 1, 0, 1, STORE, 1, 383 * 64, 64, 512, BASE | Y)
-add("STT mode 1: chunk loop at 192 tiles", 1, 1, 1, STORE, 1, 192 * 64, 64, 512, BASE | Y)
-add("STT mode 1: no chunk loop at 191 tiles", 1, 1, 1, STORE, 1, 191 * 64, 64, 512, BASE | Y)
-add("TTS mode 1: no chunk loop at 192 tiles", 0, 1, 1, STORE, 1, 192 * 64, 64, 512, BASE | Y)
-add("loop depth 2: f32 weights", 1, 0, 0, STORE, 1, 384 * 64, 64, 512, BASE | Y)
-add("loop depth 2: NT = 2 (gate)", 1, 0, 1, GATE, 2, 384 * 64, 64, 512, BASE | Y)
-add("loop depth 4: bf16 weights, NT = 1", 1, 0, 1, STORE, 1, 384 * 64, 64, 512, BASE | Y)
-add("smallk at 1024 tiles, MT 4", 1, 0, 0, STORE, 1, 1024 * 64, 64, 64, BASE | Y)
-add("no smallk at 1023 tiles, MT 4", 1, 0, 0, STORE, 1, 1023 * 64, 64, 64, BASE | Y)
-add("mode 1 split-K: M = 16 on bx3u<1>, 24 KB", 1, 1, 1, STORE, 1, 16, 2048, 2048, BASE | Y)
-add("mode 1 split-K: M = 17 on bx3u<2>, 48 KB", 1, 1, 1, STORE, 1, 17, 2048, 2048, BASE | Y)
-add("mode 1 split-K: M = 32 on bx3u<2>, 48 KB", 1, 1, 1, STORE, 1, 32, 2048, 2048, BASE | Y)
-add("mode 1 split-K: M = 65 on bx3 split", 1, 1, 1, STORE, 1, 65, 2048, 2048, BASE | Y)
-add("33..64-row override: 256 workgroups, M = 48 on two 32-row tiles", 1, 1, 1, STORE, 1, 48, 64, 256 * 256, BASE | Y)
-add("33..64-row override: 257 workgroups stay at MT 4", 1, 1, 1, STORE, 1, 48, 64, 257 * 256, BASE | Y)
-add("33..64-row override: not for the QKV epilogue", 1, 1, 1, QKV, 1, 48, 64, 256 * 256, BASE | Y)
-add("two-n-tile form at (N / 128) * grid.z = 256", 1, 1, 1, STORE, 1, 256 * 64, 128, 512, BASE | Y)
-add("no two-n-tile form at 255", 1, 1, 1, STORE, 1, 255 * 64, 128, 512, BASE | Y)
-add("whole-K gate: K = 1024, M = 64 taken", 0, 1, 1, GATE, 2, 64, 2048, 1024, BASE | Y)
-add("whole-K gate: M = 65 refused", 0, 1, 1, GATE, 2, 65, 2048, 1024, BASE | Y)
-add("whole-K gate: K = 2048 (eight chunks) refused", 0, 1, 1, GATE, 2, 64, 2048, 2048, BASE | Y)
-add("whole-K gate: N % 16 != 0 refused", 0, 1, 1, GATE, 2, 64, 2040, 1024, BASE | Y)
-add("whole-K gate: mode 0 refused", 0, 0, 1, GATE, 2, 64, 2048, 1024, BASE | Y)
-add("RVQ never on a bx3 kernel: split-K", 1, 1, 1, RVQ, 1, 64, 2048, 512, BASE | BIAS)
-add("RVQ never on a bx3 kernel: chunk loop", 1, 1, 1, RVQ, 1, 192 * 64, 2048, 512, BASE | BIAS)
-add("RVQ never on a bx3 kernel: generic", 1, 1, 1, RVQ, 1, 64, 2048, 100, BASE | BIAS)
-add("generic: chunk partials do not fit in LDS", 1, 0, 0, STORE, 1, 16, 64, 161 * 256 - 28, BASE | Y)
+def branch_rows():
+    """(a) one row per branch of plan_gemm."""
+    rows = []
+    add(rows, "generic: K % 32 != 0", 1, 0, 0, STORE, 1, 16, 64, 100, BASE | Y)
+    add(rows, "one chunk f32: tile kernel, fused epilogue, separate row norm", 1, 0, 0, STORE, 1, 16, 64, 256, BASE | Y | NORM)
+    add(rows, "two chunks mode 0: slabs left to the consumer", 1, 0, 1, STORE, 1, 16, 1024, 512, BASE | Y | MAY_DEFER)
+    add(rows, "two chunks mode 0: reduce rows<1> with the norm, N = 1024", 1, 0, 1, STORE, 1, 16, 1024, 512, BASE | Y | RES | NORM)
+    add(rows, "two chunks mode 0: reduce rows<2> with the norm, N = 2048", 1, 0, 1, STORE, 1, 16, 2048, 512, BASE | Y | RES | NORM)
+    add(rows, "two chunks mode 0: reduce rows<4> with the norm, N = 4096", 1, 0, 1, STORE, 1, 16, 4096, 512, BASE | Y | RES | NORM)
+    add(rows, "two chunks mode 0: tile reduce, no norm", 1, 0, 1, STORE, 1, 16, 1024, 512, BASE | Y)
+    add(rows, "chunk loop at 384 tiles", 1, 0, 1, STORE, 1, 384 * 64, 64, 512, BASE | Y)
+    add(rows, "no chunk loop at 383 tiles", 1, 0, 1, STORE, 1, 383 * 64, 64, 512, BASE | Y)
+    add(rows, "STT mode 1: chunk loop at 192 tiles", 1, 1, 1, STORE, 1, 192 * 64, 64, 512, BASE | Y)
+    add(rows, "STT mode 1: no chunk loop at 191 tiles", 1, 1, 1, STORE, 1, 191 * 64, 64, 512, BASE | Y)
+    add(rows, "TTS mode 1: no chunk loop at 192 tiles", 0, 1, 1, STORE, 1, 192 * 64, 64, 512, BASE | Y)
+    add(rows, "loop depth 2: f32 weights", 1, 0, 0, STORE, 1, 384 * 64, 64, 512, BASE | Y)
+    add(rows, "loop depth 2: NT = 2 (gate)", 1, 0, 1, GATE, 2, 384 * 64, 64, 512, BASE | Y)
+    add(rows, "loop depth 4: bf16 weights, NT = 1", 1, 0, 1, STORE, 1, 384 * 64, 64, 512, BASE | Y)
+    add(rows, "smallk at 1024 tiles, MT 4", 1, 0, 0, STORE, 1, 1024 * 64, 64, 64, BASE | Y)
+    add(rows, "no smallk at 1023 tiles, MT 4", 1, 0, 0, STORE, 1, 1023 * 64, 64, 64, BASE | Y)
+    add(rows, "mode 1 split-K: M = 16 on bx3u<1>, 24 KB", 1, 1, 1, STORE, 1, 16, 2048, 2048, BASE | Y)
+    add(rows, "mode 1 split-K: M = 17 on bx3u<2>, 48 KB", 1, 1, 1, STORE, 1, 17, 2048, 2048, BASE | Y)
+    add(rows, "mode 1 split-K: M = 32 on bx3u<2>, 48 KB", 1, 1, 1, STORE, 1, 32, 2048, 2048, BASE | Y)
+    add(rows, "mode 1 split-K: M = 65 on bx3 split", 1, 1, 1, STORE, 1, 65, 2048, 2048, BASE | Y)
+    add(rows, "33..64-row override: 256 workgroups, M = 48 on two 32-row tiles", 1, 1, 1, STORE, 1, 48, 64, 256 * 256, BASE | Y)
+    add(rows, "33..64-row override: 257 workgroups stay at MT 4", 1, 1, 1, STORE, 1, 48, 64, 257 * 256, BASE | Y)
+    add(rows, "33..64-row override: not for the QKV epilogue", 1, 1, 1, QKV, 1, 48, 64, 256 * 256, BASE | Y)
+    add(rows, "two-n-tile form at (N / 128) * grid.z = 256", 1, 1, 1, STORE, 1, 256 * 64, 128, 512, BASE | Y)
+    add(rows, "no two-n-tile form at 255", 1, 1, 1, STORE, 1, 255 * 64, 128, 512, BASE | Y)
+    add(rows, "whole-K gate: K = 1024, M = 64 taken", 0, 1, 1, GATE, 2, 64, 2048, 1024, BASE | Y)
+    add(rows, "whole-K gate: M = 65 refused", 0, 1, 1, GATE, 2, 65, 2048, 1024, BASE | Y)
+    add(rows, "whole-K gate: K = 2048 (eight chunks) refused", 0, 1, 1, GATE, 2, 64, 2048, 2048, BASE | Y)
+    add(rows, "whole-K gate: N % 16 != 0 refused", 0, 1, 1, GATE, 2, 64, 2040, 1024, BASE | Y)
+    add(rows, "whole-K gate: mode 0 refused", 0, 0, 1, GATE, 2, 64, 2048, 1024, BASE | Y)
+    add(rows, "RVQ never on a bx3 kernel: split-K", 1, 1, 1, RVQ, 1, 64, 2048, 512, BASE | BIAS)
+    add(rows, "RVQ never on a bx3 kernel: chunk loop", 1, 1, 1, RVQ, 1, 192 * 64, 2048, 512, BASE | BIAS)
+    add(rows, "RVQ never on a bx3 kernel: generic", 1, 1, 1, RVQ, 1, 64, 2048, 100, BASE | BIAS)
+    add(rows, "generic: chunk partials do not fit in LDS", 1, 0, 0, STORE, 1, 16, 64, 161 * 256 - 28, BASE | Y)
+    return rows
 
 
 # ---- (b) the shipped presets ----
@@ -87,38 +90,44 @@ class Conv:  # ConvGeom
         return ((self.S + self.T_in) * self.in_c, self.in_c)
 
 
-def conv(name, B, c, y=None, y2=None, res=None, stt=1, dot_mode=1):  # run_conv; y / y2 / res: a RowMap or None
+def conv(rows, name, B, c, y=None, y2=None, res=None, stt=1, dot_mode=1):  # run_conv; y / y2 / res: a RowMap or None
     bstride = (c.S + c.T_in) * c.in_c
     aligned = (c.stride * c.in_c) % 4 == 0 and bstride % 4 == 0
     f = map_flags(y is not None, y or NONE, y2 is not None, y2 or NONE, res is not None, res or NONE) | BIAS | (ALIGNED if aligned else 0)
-    add(name, stt, dot_mode, 0, STORE, 1, B * c.T_out, c.out_c, c.k * c.in_c, f)
+    add(rows, name, stt, dot_mode, 0, STORE, 1, B * c.T_out, c.out_c, c.k * c.in_c, f)
 
 
-def transformer(name, stt, dot_mode, bf16, M, T, d, hidden, gating, last_map=None, post_norm=False, ca=False):
+def transformer(rows, name, stt, dot_mode, bf16, M, T, d, hidden, gating, last_map=None, post_norm=False, ca=False):
     """One middle layer and the last layer's ff_out of transformer_forward / transformer_layer_tail."""
     lin = BASE | Y
-    add(name + " QKV", stt, dot_mode, bf16, QKV, 1, M, 3 * d, d, lin | (MAY_DEFER if T == 1 else 0))
-    add(name + " out_proj + norm", stt, dot_mode, bf16, STORE, 1, M, d, d, lin | RES | NORM)
+    add(rows, name + " QKV", stt, dot_mode, bf16, QKV, 1, M, 3 * d, d, lin | (MAY_DEFER if T == 1 else 0))
+    add(rows, name + " out_proj + norm", stt, dot_mode, bf16, STORE, 1, M, d, d, lin | RES | NORM)
     if ca:
-        add(name + " ca_q", stt, dot_mode, bf16, STORE, 1, M, d, d, lin | MAY_DEFER)
-        add(name + " ca_out + norm2", stt, dot_mode, bf16, STORE, 1, M, d, d, lin | RES | NORM)
+        add(rows, name + " ca_q", stt, dot_mode, bf16, STORE, 1, M, d, d, lin | MAY_DEFER)
+        add(rows, name + " ca_out + norm2", stt, dot_mode, bf16, STORE, 1, M, d, d, lin | RES | NORM)
     if gating:
-        add(name + " gate", stt, dot_mode, bf16, GATE, 2, M, hidden, d, lin)
+        add(rows, name + " gate", stt, dot_mode, bf16, GATE, 2, M, hidden, d, lin)
     else:
-        add(name + " ff_in", stt, dot_mode, bf16, STORE, 1, M, hidden, d, lin)
-    add(name + " ff_out + next norm1", stt, dot_mode, bf16, STORE, 1, M, d, hidden, lin | RES | NORM)
+        add(rows, name + " ff_in", stt, dot_mode, bf16, STORE, 1, M, hidden, d, lin)
+    add(rows, name + " ff_out + next norm1", stt, dot_mode, bf16, STORE, 1, M, d, hidden, lin | RES | NORM)
     if last_map is not None:  # the last layer writes the next conv's concat buffer, no norm
-        add(name + " ff_out, last layer", stt, dot_mode, bf16, STORE, 1, M, d, hidden,
+        add(rows, name + " ff_out, last layer", stt, dot_mode, bf16, STORE, 1, M, d, hidden,
             ALIGNED | RES | map_flags(True, last_map, False, (0, 0), True, plain(d)))
     elif not post_norm:
-        add(name + " ff_out, last layer", stt, dot_mode, bf16, STORE, 1, M, d, hidden, lin | RES)
+        add(rows, name + " ff_out, last layer", stt, dot_mode, bf16, STORE, 1, M, d, hidden, lin | RES)
 
 
 def gating_hidden(t):
     return 11 * t.d_model // 4 if t.dim_feedforward == 4 * t.d_model else 2 * t.dim_feedforward // 3
 
 
-def mimi_products(m, B):
+DEC = "mimi dec"  # every decoder product's name starts with it
+
+
+def mimi_products(m, B, stt=1, dot_mode=1):
+    """The matrix products of one Mimi encode step and one decode step at batch B, as rows (the decoder's are named DEC ...).
+    stt / dot_mode: the engine the Mimi belongs to (they choose the plan's default knobs, nothing else: the weights are f32)."""
+    rows = []
     FRAME = 1920
     # encoder (load_mimi, seanet_encode)
     mult, T = 1, FRAME
@@ -134,64 +143,78 @@ def mimi_products(m, B):
         mult *= 2
     final = Conv(mult * m.n_filters, m.dimension, m.last_kernel_size, 1, T, T)
     down = Conv(m.dimension, m.dimension, 2 * m.downsample_stride, m.downsample_stride, T, T // m.downsample_stride)
-    conv("mimi enc init", B, init, y=plain(init.out_c), y2=stages[0][0].cat_map())
+    e = dict(stt=stt, dot_mode=dot_mode)
+    conv(rows, "mimi enc init", B, init, y=plain(init.out_c), y2=stages[0][0].cat_map(), **e)
     for i, (ra, rb, dn) in enumerate(stages):
-        conv("mimi enc stage %d ra" % i, B, ra, y2=rb.cat_map())
-        conv("mimi enc stage %d rb" % i, B, rb, y2=dn.cat_map(), res=plain(rb.out_c))
+        conv(rows, "mimi enc stage %d ra" % i, B, ra, y2=rb.cat_map(), **e)
+        conv(rows, "mimi enc stage %d rb" % i, B, rb, y2=dn.cat_map(), res=plain(rb.out_c), **e)
         if i + 1 < len(stages):
-            conv("mimi enc stage %d down" % i, B, dn, y=plain(dn.out_c), y2=stages[i + 1][0].cat_map())
+            conv(rows, "mimi enc stage %d down" % i, B, dn, y=plain(dn.out_c), y2=stages[i + 1][0].cat_map(), **e)
         else:
-            conv("mimi enc stage %d down" % i, B, dn, y2=final.cat_map())
-    conv("mimi enc final", B, final, y=plain(m.dimension))
+            conv(rows, "mimi enc stage %d down" % i, B, dn, y2=final.cat_map(), **e)
+    conv(rows, "mimi enc final", B, final, y=plain(m.dimension), **e)
     t = m.transformer
-    transformer("mimi enc tr", 1, 1, 0, B * T, T, t.d_model, t.dim_feedforward, False, last_map=down.cat_map())
+    transformer(rows, "mimi enc tr", stt, dot_mode, 0, B * T, T, t.d_model, t.dim_feedforward, False, last_map=down.cat_map())
     f = map_flags(True, plain(m.dimension), False, NONE, False, NONE) | ALIGNED  # the downsample conv has no bias
-    add("mimi enc downsample", 1, 1, 0, STORE, 1, B * down.T_out, down.out_c, down.k * down.in_c, f)
-    add("mimi rvq input_proj", 1, 1, 0, STORE, 1, B, m.quantizer_dim, m.dimension, BASE | Y)
-    add("mimi rvq codebook", 1, 1, 0, RVQ, 1, B, m.quantizer_bins, m.quantizer_dim, BASE | BIAS)
+    add(rows, "mimi enc downsample", stt, dot_mode, 0, STORE, 1, B * down.T_out, down.out_c, down.k * down.in_c, f)
+    add(rows, "mimi rvq input_proj", stt, dot_mode, 0, STORE, 1, B, m.quantizer_dim, m.dimension, BASE | Y)
+    add(rows, "mimi rvq codebook", stt, dot_mode, 0, RVQ, 1, B, m.quantizer_bins, m.quantizer_dim, BASE | BIAS)
     # decoder (load_mimi, mimi_decode_body)
-    add("mimi dec rvq output_proj first", 1, 1, 0, STORE, 1, B, m.dimension, m.quantizer_dim, BASE | Y)
-    add("mimi dec rvq output_proj rest", 1, 1, 0, STORE, 1, B, m.dimension, m.quantizer_dim, BASE | Y | RES)
+    add(rows, DEC + " rvq output_proj first", stt, dot_mode, 0, STORE, 1, B, m.dimension, m.quantizer_dim, BASE | Y)
+    add(rows, DEC + " rvq output_proj rest", stt, dot_mode, 0, STORE, 1, B, m.dimension, m.quantizer_dim, BASE | Y | RES)
     dec_init = Conv(m.dimension, mult * m.n_filters, m.kernel_size, 1, T, T)
-    transformer("mimi dec tr", 1, 1, 0, B * T, T, t.d_model, t.dim_feedforward, False, last_map=dec_init.cat_map())
-    conv("mimi dec init", B, dec_init, y2=plain(dec_init.out_c))
+    transformer(rows, DEC + " tr", stt, dot_mode, 0, B * T, T, t.d_model, t.dim_feedforward, False, last_map=dec_init.cat_map())
+    conv(rows, DEC + " init", B, dec_init, y2=plain(dec_init.out_c), **e)
     dec = []
     for i in range(m.n_ratios):
         ratio = m.ratios[i]
         in_c = mult * m.n_filters
         out_c = in_c // 2
-        add("mimi dec stage %d convtr" % i, 1, 1, 0, STORE, 1, B * T, 2 * ratio * out_c, in_c, BASE | Y)
+        add(rows, DEC + " stage %d convtr" % i, stt, dot_mode, 0, STORE, 1, B * T, 2 * ratio * out_c, in_c, BASE | Y)
         T *= ratio
         dec.append((Conv(out_c, out_c // m.compress, m.residual_kernel_size, 1, T, T), Conv(out_c // m.compress, out_c, 1, 1, T, T)))
         mult //= 2
     dec_final = Conv(m.n_filters, m.channels, m.last_kernel_size, 1, T, T)
     for i, (ra, rb) in enumerate(dec):
-        conv("mimi dec stage %d ra" % i, B, ra, y2=rb.cat_map())
-        conv("mimi dec stage %d rb" % i, B, rb, y2=plain(rb.out_c) if i + 1 < len(dec) else dec_final.cat_map(), res=plain(rb.out_c))
-    conv("mimi dec final", B, dec_final, y=plain(m.channels))
+        conv(rows, DEC + " stage %d ra" % i, B, ra, y2=rb.cat_map(), **e)
+        conv(rows, DEC + " stage %d rb" % i, B, rb, y2=plain(rb.out_c) if i + 1 < len(dec) else dec_final.cat_map(), res=plain(rb.out_c), **e)
+    conv(rows, DEC + " final", B, dec_final, y=plain(m.channels), **e)
+    return rows
 
 
-stt = dsm_amd.config_stt_1b_en_fr()
-d, hid = stt.lm.d_model, gating_hidden(stt.lm)
-transformer("stt-1b group of 32:", 1, 1, 1, 32, 1, d, hid, True, post_norm=True)
-add("stt-1b group of 32: text linear", 1, 1, 1, STORE, 1, 32, stt.text_out_vocab_size, d, BASE | Y)
-add("stt-1b group of 32: extra heads", 1, 1, 1, STORE, 1, 32, stt.extra_heads_num * stt.extra_heads_dim, d, BASE | Y)
-mimi_products(stt.mimi, 64)
-tts = dsm_amd.config_tts_v202501()
-d, hid, D, dhid = tts.lm.d_model, gating_hidden(tts.lm), tts.depformer.d_model, gating_hidden(tts.depformer)
-transformer("tts B = 32 main LM:", 0, 1, 1, 32, 1, d, hid, True, post_norm=True, ca=True)
-add("tts B = 32 text linear", 0, 1, 1, STORE, 1, 32, tts.text_out_vocab_size, d, BASE | Y)
-add("tts B = 32 depformer in_all", 0, 1, 1, STORE, 1, 32, tts.dep_weight_groups * D, d, BASE | Y)
-transformer("tts B = 32 depformer:", 0, 1, 1, 32, 1, D, dhid, True)
-add("tts B = 32 depformer linears.k", 0, 1, 1, STORE, 1, 32, tts.audio_vocab_size - 1, D, BASE | Y | MAY_DEFER)
+def preset_rows():
+    """(b) the products of the shipped presets."""
+    rows = []
+    stt = dsm_amd.config_stt_1b_en_fr()
+    d, hid = stt.lm.d_model, gating_hidden(stt.lm)
+    transformer(rows, "stt-1b group of 32:", 1, 1, 1, 32, 1, d, hid, True, post_norm=True)
+    add(rows, "stt-1b group of 32: text linear", 1, 1, 1, STORE, 1, 32, stt.text_out_vocab_size, d, BASE | Y)
+    add(rows, "stt-1b group of 32: extra heads", 1, 1, 1, STORE, 1, 32, stt.extra_heads_num * stt.extra_heads_dim, d, BASE | Y)
+    rows += mimi_products(stt.mimi, 64)
+    tts = dsm_amd.config_tts_v202501()
+    d, hid, D, dhid = tts.lm.d_model, gating_hidden(tts.lm), tts.depformer.d_model, gating_hidden(tts.depformer)
+    transformer(rows, "tts B = 32 main LM:", 0, 1, 1, 32, 1, d, hid, True, post_norm=True, ca=True)
+    add(rows, "tts B = 32 text linear", 0, 1, 1, STORE, 1, 32, tts.text_out_vocab_size, d, BASE | Y)
+    add(rows, "tts B = 32 depformer in_all", 0, 1, 1, STORE, 1, 32, tts.dep_weight_groups * D, d, BASE | Y)
+    transformer(rows, "tts B = 32 depformer:", 0, 1, 1, 32, 1, D, dhid, True)
+    add(rows, "tts B = 32 depformer linears.k", 0, 1, 1, STORE, 1, 32, tts.audio_vocab_size - 1, D, BASE | Y | MAY_DEFER)
+    return rows
 
-lib = dsm_amd.load_library()
-buf = C.create_string_buffer(512)
-for r in rows:
+
+def plan_line(lib, r):
+    """What dsm_debug_gemm_plan answers for a row."""
+    buf = C.create_string_buffer(512)
     n = lib.dsm_debug_gemm_plan(r["stt"], r["dot_mode"], r["weight_bf16"], r["epi"], r["nt"], r["M"], r["N"], r["K"], r["flags"], buf, len(buf))
     assert n > 0, r
-    r["line"] = buf.value.decode()
-out = os.path.join(ROOT, "tests", "golden", "gemm_plans.json")
-with open(out, "w") as f:
-    f.write("[\n" + ",\n".join(json.dumps(r) for r in rows) + "\n]\n")
-print(out, len(rows), "rows")
+    return buf.value.decode()
+
+
+if __name__ == "__main__":
+    lib = dsm_amd.load_library()
+    rows = branch_rows() + preset_rows()
+    for r in rows:
+        r["line"] = plan_line(lib, r)
+    out = os.path.join(ROOT, "tests", "golden", "gemm_plans.json")
+    with open(out, "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps(r) for r in rows) + "\n]\n")
+    print(out, len(rows), "rows")
