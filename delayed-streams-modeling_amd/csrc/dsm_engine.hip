@@ -48,7 +48,7 @@ static void dsm_read_env(DsmDevice* e, bool stt) {
   e->use_graphs = dsm_env_int("DSM_GRAPHS", 1) != 0;
   e->fuse_qkv = dsm_env_int("DSM_FUSE_QKV", 1) != 0;
   e->stream_prio = dsm_env_int("DSM_STREAM_PRIO", 0) != 0;  // the TTS engine's two streams have no priorities: ignored there
-  e->fuse_front = dsm_env_int("DSM_FUSE_FRONT", 0) != 0;
+  e->fuse_front = dsm_env_int("DSM_FUSE_FRONT", 1) != 0;
   e->chunk_loop_min_tiles = dsm_env_int("DSM_CHUNK_LOOP_MIN", e->chunk_loop_min_tiles);
   e->loop_depth = dsm_env_int("DSM_LOOP_DEPTH", e->loop_depth) == 2 ? 2 : 4;
   e->smallk_min_tiles = dsm_env_int("DSM_SMALLK_MIN", e->smallk_min_tiles);

@@ -1967,7 +1967,8 @@ __global__ void extra_heads_kernel(const float* __restrict__ eh /* [B][nh*dim] *
 // workgroup reads 72 PCM samples and writes one [64][64] tile of the next conv's input.
 // Arithmetic is the GEMM path's, operation for operation (dsm_numerics.h):
 //   * init conv: K = 7 sits in lane group q = 0 of one 32-block, so the canonical chain is fmaf over taps 0..6 from +0
-//     (the zero-padded taps add +0 to an accumulator that is never -0), then + bias: VALU, no MFMA;
+//     (the zero-padded taps add +0 to an accumulator that is never -0), then + bias: VALU, no MFMA, and one scalar chain per
+//     channel (dsm_unpaired: never packed pairs);
 //   * conv k 3: K = 192 = six 32-blocks of one chunk, v_mfma_f32_16x16x4_f32 in the canonical order
 //     (k = 32 blk + 8 q + s, s outer), + bias, ELU; its im2col rows are windows of the ELU'd tile in LDS;
 //   * conv k 1: one 32-block, + bias, skip + value (the raw init-conv output, kept in LDS), ELU.
@@ -1986,6 +1987,17 @@ struct SeanetFrontArgs {
   int ld0, ld1, ld2;
   int T, S0, Sd;
 };
+
+// A value the compiler may not pair with a neighbour's into one packed operation (v_pk_fma_f32 / v_pk_add_f32); no instruction
+// is emitted.  seanet_front_kernel's init conv needs it: two channels' tap chains, paired, became a chain of DEPENDENT
+// v_pk_fma_f32 whose taps wait for their LDS operand in between, and the compiler counts that s_waitcnt as the wait state a
+// packed-f32 result needs before a dependent vector instruction reads it.  A wait that is already satisfied takes no issue
+// cycle; the next tap then read the low half of the accumulator pair before the tap in front had written it, and one row of
+// sixteen lanes lost that tap in channel 4 cq.  Scalar v_fma_f32 / v_fmac_f32 are fully interlocked.
+__device__ __forceinline__ float dsm_unpaired(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
 
 template <int TM>
 constexpr size_t seanet_front_lds() { return sizeof(float) * ((TM + 2) * 64 + TM * 64 + TM * 32 + (TM + 2 + 7 - 1)); }
@@ -2034,8 +2046,8 @@ __global__ __launch_bounds__(256) void seanet_front_kernel(SeanetFrontArgs a) {
       for (int j = 0; j < 4; ++j) {
         float acc = 0.0f;
 #pragma unroll
-        for (int sidx = 0; sidx < TAPS0; ++sidx) acc = DSM_FMAF(w0r[j][sidx], xr[sidx], acc);
-        yv[j] = a.b0 ? acc + b0r[j] : acc;
+        for (int sidx = 0; sidx < TAPS0; ++sidx) acc = dsm_unpaired(DSM_FMAF(w0r[j][sidx], xr[sidx], acc));
+        yv[j] = a.b0 ? dsm_unpaired(acc + b0r[j]) : acc;
       }
       ev = make_float4(dsm_elu(yv[0]), dsm_elu(yv[1]), dsm_elu(yv[2]), dsm_elu(yv[3]));
       if (R >= 2) *reinterpret_cast<float4*>(&y0[(R - 2) * C0 + 4 * (cq ^ ((R - 2) & 15))]) = make_float4(yv[0], yv[1], yv[2], yv[3]);

@@ -35,8 +35,8 @@
  *     DSM_LOOP_DEPTH      4     2: those GEMMs' rolling load window holds two blocks instead of four
  *     DSM_SMALLK_MIN      1024  one-chunk GEMMs (K <= 256) run on the loop kernel from this many 64-row tiles on
  *     DSM_SMALLK_MT       4     16-row tiles per workgroup of those launches (1, 2 or 4)
- *     DSM_FUSE_FRONT      0     1: the SEANet front end as one fused kernel (not bit-reproducible beside dot_mode 1 LM
- *                               kernels on the same CUs: DESIGN.md section 8)
+ *     DSM_FUSE_FRONT      1     0: the SEANet front end as three GEMM launches instead of the one fused kernel (same bits;
+ *                               what tests compare the fused kernel against)
  */
 #ifndef DSM_H
 #define DSM_H
