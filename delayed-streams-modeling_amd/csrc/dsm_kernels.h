@@ -2426,7 +2426,9 @@ __global__ void spk_rope_table_kernel(float* __restrict__ cs, const float* __res
 //   3. softmax per query by its 16 lanes: lane chains of max, exp and sum over keys lane, lane + 16, ..., a 16-lane xor
 //      butterfly, the weights divided by the sum once;
 //   4. value tiles of 64 rows into LDS, thread (query, dims lane + 16 i) chains weight * v over the keys in ascending order.
-// Every sum has one order that depends on T alone.  cs null: no positional embedding inside the transformer, q and k are used as
+// Every sum has one order that depends on T alone, and every chain is scalar (dsm_unpaired on the rotation's products, the QK
+// dot and the PV accumulators: paired, they were dependent v_pk_fma_f32 / v_pk_add_f32 with at most an s_waitcnt in between,
+// the sequence that lost taps in seanet_front_kernel; tools/packed_f32_hazards.py keeps the library free of it).  cs null: no positional embedding inside the transformer, q and k are used as
 // they are.  K and V of one head at T = 250, HD = 64 are 128 KB: they pass through a 16.6 KB tile instead, so the launch stays
 // inside the default 64 KB of dynamic LDS up to T = 700 at HD = 64 (860 at HD = 32; spk_attn_lds); attach refuses a longer context.
 #define SPK_QB 16
@@ -2454,7 +2456,7 @@ __global__ __launch_bounds__(256) void spk_attn_kernel(float* __restrict__ out, 
       const int r = e / (HD / 2), p = e % (HD / 2);
       const float2 x = *reinterpret_cast<const float2*>(base + (long)(r0 + r) * 3 * d + part * d + 2 * p);
       const float2 c = cs ? *reinterpret_cast<const float2*>(cs + ((long)(r0 + r) * (HD / 2) + p) * 2) : make_float2(1.0f, 0.0f);
-      const float t0 = x.x * c.x, t1 = x.y * c.y, t2 = x.x * c.y, t3 = x.y * c.x;
+      const float t0 = dsm_unpaired(x.x * c.x), t1 = dsm_unpaired(x.y * c.y), t2 = dsm_unpaired(x.x * c.y), t3 = dsm_unpaired(x.y * c.x);
       dst[r * ld + 2 * p] = t0 - t1;
       dst[r * ld + 2 * p + 1] = t2 + t3;
     }
@@ -2474,7 +2476,7 @@ __global__ __launch_bounds__(256) void spk_attn_kernel(float* __restrict__ out, 
         if (jl < nk) {
           float p = 0.0f;
 #pragma unroll 8
-          for (int dd = 0; dd < HD; ++dd) p = DSM_FMAF(qs[qi * HD + dd], kv[jl * (HD + 1) + dd], p);
+          for (int dd = 0; dd < HD; ++dd) p = dsm_unpaired(DSM_FMAF(qs[qi * HD + dd], kv[jl * (HD + 1) + dd], p));
           sc[qi * Tp + j] = j <= qpos ? p * scale : -DSM_INF_F;
         }
       }
@@ -2515,7 +2517,7 @@ __global__ __launch_bounds__(256) void spk_attn_kernel(float* __restrict__ out, 
       for (int j = 0; j < nk; ++j) {
         const float wj = w[j];
 #pragma unroll
-        for (int i = 0; i < HD / 16; ++i) acc[i] = DSM_FMAF(wj, kv[j * (HD + 1) + kl + 16 * i], acc[i]);
+        for (int i = 0; i < HD / 16; ++i) acc[i] = dsm_unpaired(DSM_FMAF(wj, kv[j * (HD + 1) + kl + 16 * i], acc[i]));
       }
     }
   }

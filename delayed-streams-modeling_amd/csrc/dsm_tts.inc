@@ -967,8 +967,10 @@ int dsm_tts_debug_read(dsm_tts* t, const char* name, float* out, size_t cap) {
   if (n > cap) n = cap;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
+  // the copy rides the model stream: a null-stream hipMemcpy queues behind whatever other engines of the process have enqueued on
+  // the hardware queue it lands on (166 ms behind a B = 64 STT engine's queued steps, profiles/r11/packed_f32.txt)
+  HIPCHK(hipMemcpyAsync(out, src, sizeof(float) * n, hipMemcpyDeviceToHost, e->s_model));
   HIPCHK(hipStreamSynchronize(e->s_model));
-  HIPCHK(hipMemcpy(out, src, sizeof(float) * n, hipMemcpyDeviceToHost));
   return (int)n;
 }
 

@@ -4,16 +4,12 @@ VGPRs USED (NumVgprs + NumAgprs) against VGPRs ALLOCATED (NumVGPRsForWavesPerEU,
 static LDS, scratch (spills), occupancy as the compiler sees it.  A static LDS array that bounds the occupancy makes the compiler
 pad the allocation up to that occupancy (r04: 136 allocated for 88 used) — registers other streams' workgroups cannot use beside the
 kernel; such rows are flagged PADDED.  usage: tools/kernel_resources.py [substring ...]   (takes about 80 s: one device compile)"""
-import os, re, subprocess, sys, tempfile
+import os, re, sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "delayed-streams-modeling_amd", "csrc", "dsm_engine.hip")
-hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-with tempfile.TemporaryDirectory() as d:
-    asm = os.path.join(d, "dsm.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I" + os.path.join(ROOT, "include"),
-                    "-S", "--cuda-device-only", "-o", asm, SRC], check=True, stderr=subprocess.DEVNULL)
-    s = open(asm).read()
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from device_asm import compile_device_asm, kernel_name
+
+s = compile_device_asm()
 rows = []
 for m in re.finditer(r"; Kernel info:\n(.*?); Occupancy: (\d+)", s, re.S):
     blk = m.group(1)
@@ -22,9 +18,7 @@ for m in re.finditer(r"; Kernel info:\n(.*?); Occupancy: (\d+)", s, re.S):
     names = re.findall(r"\.set (\S+)\.has_indirect_call", pre)
     if not names:
         continue
-    name = subprocess.run(["c++filt", names[-1]], capture_output=True, text=True).stdout.strip()
-    name = name.replace("unsigned short", "bf16").replace("void ", "")
-    name = re.sub(r"\(.*", "", name)
+    name = kernel_name(names[-1])
     rows.append((name, get("TotalNumVgprs"), get("NumVGPRsForWavesPerEU"), get("LDSByteSize"), get("ScratchSize"), int(m.group(2))))
 subs = sys.argv[1:]
 print(f"{'kernel':64s} {'used':>5s} {'alloc':>5s} {'LDS':>6s} {'scr':>4s} occ")
