@@ -8,6 +8,7 @@ missing, calls raise.
 The directory name carries a hyphen (it mirrors the upstream repo name), so import it through
 the `dsm_amd` shim at the repo root.
 """
+import collections
 import ctypes as C
 import os
 import numpy as np
@@ -134,7 +135,26 @@ ABI_SYMBOLS = [
     "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot", "dsm_tts_debug_read", "dsm_tts_get_metrics", "dsm_tts_set_sampling",
     "dsm_tts_set_ca_src", "dsm_tts_attach_mimi", "dsm_tts_step_pcm", "dsm_tts_recv_pcm", "dsm_tts_pcm_pending",
     "dsm_tts_attach_speaker_encoder", "dsm_tts_encode_voice", "dsm_tts_speaker_empty",
+    "dsm_tts_request_begin", "dsm_tts_request_push_words", "dsm_tts_request_close", "dsm_tts_run", "dsm_tts_collect",
+    "dsm_tts_request_status",
 ]
+TTS_RUN_MAX = 16  # DSM_TTS_RUN_MAX
+TTS_REQ_IDLE, TTS_REQ_RUNNING, TTS_REQ_WAITING, TTS_REQ_DONE, TTS_REQ_DONE_LIMIT = range(5)  # DSM_TTS_REQ_*
+
+
+class TtsWordEvent(C.Structure):
+    """dsm_tts_word_event: steps, not seconds (divide by 12.5, srv/tts.rs:599-600); word -1 is the initial empty word."""
+    _fields_ = [("slot", C.c_int), ("word", C.c_int), ("start_step", C.c_int), ("stop_step", C.c_int)]
+
+
+class TtsBlockC(C.Structure):
+    """dsm_tts_block (include/dsm.h): caller-provided arrays of one dsm_tts_run block."""
+    _fields_ = [("n_steps", C.c_int), ("stepped", C.c_void_p), ("text_token", C.c_void_p), ("audio", C.c_void_p),
+                ("pcm", C.c_void_p), ("pcm_valid", C.c_void_p), ("events", C.POINTER(TtsWordEvent)),
+                ("events_cap", C.c_int), ("n_events", C.c_int), ("status", C.c_void_p)]
+
+
+TtsBlock = collections.namedtuple("TtsBlock", "n_steps stepped text_token audio pcm pcm_valid events status")
 PROF_TAGS = ["attn_lm", "gemm_lm", "attn_mimi", "gemm_mimi", "rvq", "other"]
 
 _lib = None
@@ -276,6 +296,12 @@ def load_library(path=None):
     lib.dsm_tts_attach_speaker_encoder.argtypes = [vp, C.c_int, C.c_char_p]
     lib.dsm_tts_encode_voice.argtypes = [vp, fp, C.c_int, C.c_int, fp, C.c_int, C.POINTER(C.c_int)]
     lib.dsm_tts_speaker_empty.argtypes = [vp, fp, C.c_int, C.POINTER(C.c_int)]
+    lib.dsm_tts_request_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.dsm_tts_request_push_words.argtypes = [vp, C.c_int, u32p, vp, C.c_int]
+    lib.dsm_tts_request_close.argtypes = [vp, C.c_int]
+    lib.dsm_tts_run.argtypes = [vp, C.c_int, C.c_int]
+    lib.dsm_tts_collect.argtypes = [vp, C.POINTER(TtsBlockC)]
+    lib.dsm_tts_request_status.argtypes = [vp, C.c_int]
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
         getattr(lib, name).restype = C.c_int
@@ -977,6 +1003,50 @@ class TtsEngine:
         out, rows = np.zeros((cap, cond), dtype=np.float32), C.c_int(0)
         self._check(self.lib.dsm_tts_speaker_empty(self.h, _ptr(out), cap, C.byref(rows)))
         return out[:rows.value]
+
+    # ---- a request's text schedule on the device (srv/tts.rs:574-621), K steps per visit ----
+    def request_begin(self, slot, max_seq_len, extra_steps=0):
+        """Starts a request on a fresh slot (reset_batch_idx, then set_ca_src / set_sampling as needed)."""
+        self._check(self.lib.dsm_tts_request_begin(self.h, slot, max_seq_len, extra_steps))
+
+    def push_words(self, slot, words):
+        """in_tx.send(Some(word_tokens)) for each word: a list of token lists (a word may be empty); the caller puts the
+        bos token in front of the first word's tokens (srv/tts.rs:484-493)."""
+        lens = np.array([len(w) for w in words], dtype=np.int32)
+        toks = np.array([t for w in words for t in w], dtype=np.uint32)
+        self._check(self.lib.dsm_tts_request_push_words(self.h, slot, _ptr(toks) if toks.size else None, _ptr(lens), len(words)))
+
+    def request_close(self, slot):
+        """in_tx.send(None): no more words."""
+        self._check(self.lib.dsm_tts_request_close(self.h, slot))
+
+    def run(self, n_steps, decode=False):
+        """Enqueues n_steps (1..TTS_RUN_MAX) steps of every slot with a request; nothing is read back until collect()."""
+        self._check(self.lib.dsm_tts_run(self.h, n_steps, 1 if decode else 0))
+        self._run = (n_steps, bool(decode))
+
+    def collect(self):
+        """Waits for the block.  Returns TtsBlock: stepped [n][B], text_token [n][B], audio [n][B][S], pcm [n][B][1920] and
+        pcm_valid [n][B] (None unless run(decode=True)), events [(slot, word, start_step, stop_step)], status [B]."""
+        n, decode = getattr(self, "_run", None) or (TTS_RUN_MAX, False)
+        B = self.B
+        stepped = np.zeros((n, B), dtype=np.uint8)
+        text = np.zeros((n, B), dtype=np.uint32)
+        audio = np.zeros((n, B, self.S), dtype=np.uint32)
+        pcm = np.zeros((n, B, FRAME_SIZE), dtype=np.float32) if decode else None
+        valid = np.zeros((n, B), dtype=np.uint8) if decode else None
+        status = np.zeros(B, dtype=np.int32)
+        ev = (TtsWordEvent * (n * B))()
+        blk = TtsBlockC(0, _ptr(stepped), _ptr(text), _ptr(audio), _ptr(pcm), _ptr(valid), ev, n * B, 0, _ptr(status))
+        self._check(self.lib.dsm_tts_collect(self.h, C.byref(blk)))
+        self._run = None
+        k = blk.n_steps
+        events = [(e.slot, e.word, e.start_step, e.stop_step) for e in ev[:blk.n_events]]
+        return TtsBlock(k, stepped[:k], text[:k], audio[:k], None if pcm is None else pcm[:k],
+                        None if valid is None else valid[:k], events, status)
+
+    def request_status(self, slot):
+        return self._check(self.lib.dsm_tts_request_status(self.h, slot))
 
     def set_ca_src(self, slot, ca_src, ca_src_uncond=None, cfg_alpha=0.0):
         """State::new's ca_src / cfg_alpha for the slot (srv/tts.rs:426-441): ca_src [n][ca_dim] f32 or None;

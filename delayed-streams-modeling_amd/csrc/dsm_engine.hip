@@ -1097,6 +1097,7 @@ int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, 
 
 #include "dsm_engine_api.inc"
 #include "dsm_tts.inc"
+#include "dsm_tts_request.inc"
 #include "dsm_speaker.inc"
 #include "dsm_audio.inc"
 #include "dsm_worker.inc"

@@ -2361,6 +2361,164 @@ __global__ void tts_frame_kernel(TtsFrameArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The TTS request loop on the device (dsm_tts_request.inc): the inference loop of srv/tts.rs:574-621 and the integer
+// bookkeeping of State::step (core/tts_streaming.rs:126-158,195-237) per slot, so that the host can enqueue K steps without
+// reading a result.  Two launches per step on the model stream, outside the groups' graphs (the step of the block is a
+// launch argument): tts_sched_kernel in front of the groups, tts_commit_kernel behind their join.  One thread per slot,
+// plain stores.
+// ------------------------------------------------------------------------------------------
+enum { TTS_REQ_IDLE = 0, TTS_REQ_RUNNING = 1, TTS_REQ_WAITING = 2, TTS_REQ_DONE = 3, TTS_REQ_DONE_LIMIT = 4 };  // == DSM_TTS_REQ_*
+struct TtsReqState {  // one per slot, in HBM
+  int32_t status;
+  int32_t step;       // State::step_idx == the loop's step_idx
+  int32_t cur_word;   // push-order index of the current word; -1: the initial empty word (srv/tts.rs:577)
+  int32_t has_word;   // 0: word_tokens == None (the queue was closed and drained)
+  int32_t token_idx, step_past_last, last_epad;
+  uint32_t last_text;  // the loop's last_text_token: the next step's prev_text_token
+  int32_t cpads;       // State::consecutive_pads
+  int32_t max_seq_len, extra_steps;
+  int32_t n_words, closed;  // the queue: words pushed so far; in_tx.send(None) was seen
+};
+// A step's record of one slot in the block buffer: TTS_REC_HDR int32 then the S audio tokens.
+enum { TTS_REC_STEPPED = 0, TTS_REC_RUN = 1, TTS_REC_TEXT = 2, TTS_REC_OVW = 3, TTS_REC_EV = 4, TTS_REC_EV_WORD = 5,
+       TTS_REC_EV_START = 6, TTS_REC_EV_STOP = 7, TTS_REC_HDR = 8 };
+struct TtsSchedArgs {
+  TtsReqState* req;        // [B]
+  const uint32_t* q_tok;   // [B][qcap] the words' tokens back to back
+  const int32_t* q_end;    // [B][qcap] end offset of word w in q_tok (its start is the end of word w - 1)
+  int qcap;
+  int32_t* rec;            // this step's records [B][rec_ld]
+  int rec_ld;
+  // what dsm_tts_step uploads: tokens [R][1 + nc], allowed [B], the flag block
+  int32_t* tokens;
+  int32_t* allowed;
+  uint8_t *mask, *force, *run, *forced, *rmask, *rrun, *ca_act, *fsel;
+  int32_t* step;
+  const uint32_t* lat;     // [B][S] the slot's last depformer samples: row step - 1 of its token table, codebook 0, and row
+                           // step - 1 - acoustic_delay, codebooks >= 1 (the rows input assembly reads, :138,148)
+  const uint32_t* row0;    // [B][S] row 0's codebooks >= 1 (tts_frame_kernel keeps them: the write-back clamps to row 0)
+  const uint8_t* cfg_on;   // [B]
+  const uint8_t* ca_has;   // [R] the batch row has a cross-attention source
+  int B, rps, nc, S, ad, tad, max_cpads, text_in_vocab, n_steps /* rows of the token table: the engine's own limit */;
+  uint32_t pad;            // audio pad token
+  int sel;                 // frame buffer this step fills
+};
+__global__ void tts_sched_kernel(TtsSchedArgs a) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.B) return;
+  if (b == 0) *a.fsel = (uint8_t)a.sel;
+  TtsReqState r = a.req[b];
+  int32_t* rec = a.rec + (long)b * a.rec_ld;
+  int ovw = 0;
+  if (r.status == TTS_REQ_WAITING) {  // in_rx.recv() of srv/tts.rs:606, resolved once the word (or the close) has arrived
+    if (r.cur_word + 1 < r.n_words) { r.cur_word += 1; r.status = TTS_REQ_RUNNING; }
+    else if (r.closed) { r.has_word = 0; r.status = TTS_REQ_RUNNING; ovw = 1; }  // :607-610, on the previous step's text token
+  }
+  bool steps = false;
+  int32_t al = -1;
+  if (r.status == TTS_REQ_RUNNING) {
+    if (r.step >= r.max_seq_len || r.step + 1 >= a.n_steps) {  // `for step_idx in 0..max_seq_len`; the step that would bail with "max step-idx reached"
+      r.status = TTS_REQ_DONE_LIMIT;
+    } else if (!r.has_word) {  // :582-588
+      r.step_past_last += 1;
+      if (r.step_past_last > r.extra_steps + a.tad) r.status = TTS_REQ_DONE;
+      else steps = true;  // Pad
+    } else {  // :589-592
+      const int32_t* qe = a.q_end + (long)b * a.qcap;
+      const int w0 = r.cur_word > 0 ? qe[r.cur_word - 1] : 0;
+      const int w1 = r.cur_word >= 0 ? qe[r.cur_word] : 0;
+      al = r.token_idx < w1 - w0 ? (int32_t)a.q_tok[(long)b * a.qcap + w0 + r.token_idx] : -2;  // Text(id) : PadOrEpad
+      steps = true;
+    }
+  }
+  a.req[b] = r;
+  rec[TTS_REC_STEPPED] = steps ? 1 : 0;
+  rec[TTS_REC_RUN] = 0;
+  rec[TTS_REC_TEXT] = 0;
+  rec[TTS_REC_OVW] = ovw;
+  rec[TTS_REC_EV] = 0;
+  // input assembly — core/tts_streaming.rs:126-158; a slot that does not step gets what the host writes for a masked-off one
+  const int s = r.step, nc = a.nc;
+  const bool run = steps && s >= a.tad;
+  int32_t* tk = a.tokens + (long)b * a.rps * (1 + nc);
+  tk[0] = steps && r.last_text < (uint32_t)a.text_in_vocab ? (int32_t)r.last_text : 0;
+  for (int cb = 0; cb < nc; ++cb) {
+    int32_t tok = -1;  // None
+    if (steps && cb < a.S) {
+      if (cb == 0) {
+        if (s == 0) tok = (int32_t)a.pad;
+        else if (s > a.tad) tok = (int32_t)a.lat[(long)b * a.S];
+      } else if (s <= a.ad) tok = (int32_t)a.pad;
+      else if (s > a.tad + a.ad) tok = (int32_t)(s == a.ad + 1 ? a.row0[(long)b * a.S + cb] : a.lat[(long)b * a.S + cb]);
+    }
+    tk[1 + cb] = tok;
+  }
+  for (int j = 1; j < a.rps; ++j)
+    for (int i = 0; i < 1 + nc; ++i) tk[(long)j * (1 + nc) + i] = tk[i];
+  a.allowed[b] = al;
+  a.mask[b] = steps ? 1 : 0;
+  a.force[b] = r.cpads > a.max_cpads ? 1 : 0;
+  a.run[b] = run ? 1 : 0;
+  a.forced[b] = s < a.ad ? 1 : 0;
+  a.step[b] = s;
+  for (int j = 0; j < a.rps; ++j) {
+    const int row = b * a.rps + j;
+    const bool on = j == 0 || a.cfg_on[b];
+    a.rmask[row] = steps && on ? 1 : 0;
+    a.rrun[row] = run && on ? 1 : 0;
+    a.ca_act[row] = steps && on && a.ca_has[row] ? 1 : 0;
+  }
+}
+
+struct TtsCommitArgs {
+  TtsReqState* req;
+  int32_t* rec;
+  int rec_ld;
+  const uint8_t *mask, *run;
+  const uint32_t* text_token;  // [B] what the text-token rule returned
+  const uint32_t* lat;         // [B][S]
+  int B, S;
+  uint32_t text_pad, text_eop;
+};
+// What follows State::step's sampling (core/tts_streaming.rs:195-237) and the loop body behind it (srv/tts.rs:596-614).  The
+// token table itself stays on the host (the record carries what its write-back needs); the rows the next input assembly reads
+// are the slot's samples in `lat`, which only a step of this slot rewrites.
+__global__ void tts_commit_kernel(TtsCommitArgs a) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.B) return;
+  int32_t* rec = a.rec + (long)b * a.rec_ld;
+  const bool run = a.mask[b] && a.run[b];
+  for (int k = 0; k < a.S; ++k) rec[TTS_REC_HDR + k] = (int32_t)(run ? a.lat[(long)b * a.S + k] : 0xFFFFFFFFu);
+  if (!a.mask[b]) return;
+  TtsReqState r = a.req[b];
+  const uint32_t tok = a.text_token[b];
+  r.cpads = tok == a.text_pad ? r.cpads + 1 : 0;
+  rec[TTS_REC_RUN] = run ? 1 : 0;
+  rec[TTS_REC_TEXT] = (int32_t)tok;
+  if (tok == a.text_eop) {  // the value decides, whatever rule produced it: a pushed Text(eop) ends the word too
+    if (r.has_word) {
+      rec[TTS_REC_EV] = 1;
+      rec[TTS_REC_EV_WORD] = r.cur_word;
+      rec[TTS_REC_EV_START] = r.last_epad;
+      rec[TTS_REC_EV_STOP] = r.step;
+      if (r.cur_word + 1 < r.n_words) r.cur_word += 1;
+      else if (r.closed) { r.has_word = 0; rec[TTS_REC_OVW] = rec[TTS_REC_OVW] | 2; }  // overwrite_last_text_token(pad) on THIS step's token
+      else r.status = TTS_REQ_WAITING;
+    }
+    r.last_epad = r.step;
+    r.token_idx = 0;
+  } else if (tok != a.text_pad) {
+    r.token_idx += 1;
+  }
+  r.last_text = tok;  // the loop variable keeps the end-of-pad (:609 rewrites the table only)
+  r.step += 1;
+  a.req[b] = r;
+}
+// request_begin / reset, and the queue's counters: the value travels in the launch, so a later push cannot be seen early
+__global__ void tts_req_init_kernel(TtsReqState* dst, TtsReqState v) { *dst = v; }
+__global__ void tts_req_store_kernel(int32_t* dst, int32_t v) { *dst = v; }
+
+// ------------------------------------------------------------------------------------------
 // Speaker encoder (dsm_speaker.inc): the whole-clip, non-streaming Mimi encode of SpeakerEncoder::encode —
 // core/tts_streaming.rs:382-409.  Tolerance-pinned, not bit-pinned: the oracle has only the streaming Mimi.
 // ------------------------------------------------------------------------------------------

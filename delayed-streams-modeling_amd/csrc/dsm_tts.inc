@@ -99,8 +99,8 @@ struct dsm_tts : DsmDevice {
   size_t flags_bytes = 0, step_off = 0;  // the per-step upload: size, offset of the step indices (the buffer byte follows them)
   int32_t* d_step = nullptr;
   uint8_t* d_fsel = nullptr;
-  uint32_t *d_ring = nullptr, *d_row0 = nullptr, *d_fcodes = nullptr;  // [B][ad + 1], [B][S], [3][B][S]
-  uint8_t* d_fvalid = nullptr;                                          // [3][B]
+  uint32_t *d_ring = nullptr, *d_row0 = nullptr, *d_fcodes = nullptr;  // [B][ad + 1], [B][S], [kFrameBufs][B][S]
+  uint8_t* d_fvalid = nullptr;                                          // [kFrameBufs][B]
   bool mimi = false;  // mimi_w and dec are loaded: dsm_tts_step_pcm is available
   MimiW mimi_w;
   MimiDecState dec;
@@ -115,6 +115,26 @@ struct dsm_tts : DsmDevice {
   uint64_t pcm_seq = 0;  // step_pcm calls so far: entry / frame buffer of call n is n & 1
   int pcm_pending = 0;   // entries queued and not yet delivered (the oldest is (pcm_seq - pcm_pending) & 1)
   SpkEnc spk;            // voice clips -> cross-attention rows (dsm_tts_attach_speaker_encoder, dsm_speaker.inc)
+  // ---- a request's text schedule on the device, K steps per visit (dsm_tts_request.inc) ----
+  // Frames of a block: every step of a block fills a frame buffer and a pinned PCM entry of its own (buffers 3 .. 3 +
+  // DSM_TTS_RUN_MAX - 1 of d_fcodes / d_fvalid, blk_pcm[s]) — no event wait holds the model stream back for the decode stream.
+  static constexpr int kFrameBufs = 3 + DSM_TTS_RUN_MAX;
+  TtsReqState *d_req = nullptr, *h_req = nullptr;  // [B]; the pinned copy is what the last collect read
+  int qcap = 0;                                    // tokens, and words, a request's queue holds: n_steps
+  uint32_t *d_qtok = nullptr, *h_qtok = nullptr;   // [B][qcap]; the pinned mirror is append-only per request (uploads read it later)
+  int32_t *d_qend = nullptr, *h_qend = nullptr;    // [B][qcap]
+  struct ReqHost {
+    bool active = false, closed = false;
+    int n_words = 0, n_tok = 0;
+    int status = 0;  // DSM_TTS_REQ_* as of the last collect
+  };
+  std::vector<ReqHost> reqs;
+  int rec_ld = 0;                                  // TTS_REC_HDR + S
+  int32_t *d_blk = nullptr, *h_blk = nullptr;      // [DSM_TTS_RUN_MAX][B][rec_ld] the block's records
+  uint8_t *d_ca_has = nullptr, *h_ca_has = nullptr;  // [R] ca_len > 0, uploaded per block
+  PcmEntry blk_pcm[DSM_TTS_RUN_MAX];
+  int blk_pending = 0;    // steps of the block that waits for dsm_tts_collect (0: none)
+  bool blk_decode = false;
 };
 
 namespace {
@@ -289,8 +309,8 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
   t->d_fsel = t->d_mask + t->step_off + sizeof(int32_t) * (size_t)B;
   if ((rc = e->dalloc(&t->d_ring, (size_t)B * (c.acoustic_delay + 1)))) return rc;
   if ((rc = e->dalloc(&t->d_row0, (size_t)B * S))) return rc;
-  if ((rc = e->dalloc(&t->d_fcodes, (size_t)3 * B * S))) return rc;
-  if ((rc = e->dalloc(&t->d_fvalid, (size_t)3 * B))) return rc;
+  if ((rc = e->dalloc(&t->d_fcodes, (size_t)dsm_tts::kFrameBufs * B * S))) return rc;
+  if ((rc = e->dalloc(&t->d_fvalid, (size_t)dsm_tts::kFrameBufs * B))) return rc;
   t->d_force_eop = t->d_mask + B;
   t->d_run = t->d_mask + 2 * B;
   t->d_forced = t->d_mask + 3 * B;
@@ -368,6 +388,21 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
   if ((rc = e->halloc(&t->h_text_token, (size_t)B))) return rc;
   if ((rc = e->halloc(&t->h_lat, (size_t)B * S))) return rc;
   t->n_steps = (size_t)c.max_steps + c.acoustic_delay;
+  {  // the request loop's device state (dsm_tts_request.inc); zero = every slot IDLE
+    t->qcap = (int)t->n_steps;
+    t->rec_ld = TTS_REC_HDR + S;
+    if ((rc = e->dalloc(&t->d_req, B))) return rc;
+    if ((rc = e->halloc(&t->h_req, (size_t)B))) return rc;
+    if ((rc = e->dalloc(&t->d_qtok, (size_t)B * t->qcap))) return rc;
+    if ((rc = e->halloc(&t->h_qtok, (size_t)B * t->qcap))) return rc;
+    if ((rc = e->dalloc(&t->d_qend, (size_t)B * t->qcap))) return rc;
+    if ((rc = e->halloc(&t->h_qend, (size_t)B * t->qcap))) return rc;
+    if ((rc = e->dalloc(&t->d_blk, (size_t)DSM_TTS_RUN_MAX * B * t->rec_ld))) return rc;
+    if ((rc = e->halloc(&t->h_blk, (size_t)DSM_TTS_RUN_MAX * B * t->rec_ld))) return rc;
+    if ((rc = e->dalloc(&t->d_ca_has, R))) return rc;
+    if ((rc = e->halloc(&t->h_ca_has, (size_t)R))) return rc;
+    t->reqs.assign(B, dsm_tts::ReqHost{});
+  }
   t->items.resize(B);
   for (auto& it : t->items) {
     it.audio_tokens.assign(t->n_steps * S, DSM_TTS_UNGENERATED);
@@ -568,6 +603,7 @@ int tts_deliver_pcm(dsm_tts* t, float* pcm_out, uint8_t* pcm_valid_out) {
 
 namespace {
 int spk_debug_read(dsm_tts* t, const char* name, float* out, size_t cap);  // dsm_speaker.inc
+int tts_request_end(dsm_tts* t, int slot);                                  // dsm_tts_request.inc
 }
 
 extern "C" {
@@ -599,6 +635,10 @@ int tts_step_impl(dsm_tts* t, const uint32_t* prev_text_token, const int32_t* al
   const int B = t->B, S = c.dep_num_slices, nc = c.audio_codebooks;
   const uint32_t pad = (uint32_t)c.audio_vocab_size - 1, UNG = DSM_TTS_UNGENERATED;
   hipStream_t st = e->s_model;
+  // the request loop (dsm_tts_request.inc) owns the step's device buffers while a block waits, and its slots' state always
+  if (t->blk_pending) { e->set_error("a block of %d steps waits for dsm_tts_collect", t->blk_pending); return DSM_ERR_STATE; }
+  for (int b = 0; b < B; ++b)
+    if (mask[b] && t->reqs[b].active) { e->set_error("slot %d has a request: dsm_tts_run steps it", b); return DSM_ERR_STATE; }
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   const int rps = t->rps, R = t->R;
@@ -746,6 +786,11 @@ int dsm_tts_attach_mimi(dsm_tts* t, const dsm_mimi_config* mimi, const char* mim
   if ((rc = e->dalloc(&t->dec.started, B))) return rc;
   if ((rc = e->new_event(&t->ev_frames))) return rc;
   for (dsm_tts::PcmEntry& en : t->pcm_q) {
+    if ((rc = e->new_event(&en.ev))) return rc;
+    if ((rc = e->halloc(&en.h_pcm, (size_t)B * DSM_FRAME_SIZE))) return rc;
+    if ((rc = e->halloc(&en.h_valid, (size_t)B))) return rc;
+  }
+  for (dsm_tts::PcmEntry& en : t->blk_pcm) {  // one per step of a dsm_tts_run block
     if ((rc = e->new_event(&en.ev))) return rc;
     if ((rc = e->halloc(&en.h_pcm, (size_t)B * DSM_FRAME_SIZE))) return rc;
     if ((rc = e->halloc(&en.h_valid, (size_t)B))) return rc;
@@ -930,6 +975,9 @@ int dsm_tts_set_ca_src(dsm_tts* t, int slot, const float* ca_src, int n, const f
 
 int dsm_tts_reset_slot(dsm_tts* t, int slot) {
   if (!t || slot < 0 || slot >= t->B) return DSM_ERR_INVALID;
+  if (t->blk_pending) { t->set_error("a block of %d steps waits for dsm_tts_collect", t->blk_pending); return DSM_ERR_STATE; }
+  if (t->reqs[slot].active)  // ends the slot's request: IDLE again
+    if (int rc = tts_request_end(t, slot)) return rc;
   if (t->samp_k[slot] > 0)  // a fresh State has fresh (ArgMax) processors until the caller configures them again
     if (int rc = dsm_tts_set_sampling(t, slot, 0, 0.0f, 0)) return rc;
   if (t->cfg.cross_attention)  // ... and whatever ca_src / cfg_alpha its creator passes: none until dsm_tts_set_ca_src

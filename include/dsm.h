@@ -420,6 +420,63 @@ int dsm_tts_attach_speaker_encoder(dsm_tts*, int n_speakers, const char* lm_safe
 int dsm_tts_encode_voice(dsm_tts*, const float* pcm /* host [n_clips][clip_len], 24 kHz */, int n_clips, int clip_len,
                          float* ca_src_out /* host [rows][cond_dim] */, int cap_rows, int* rows_out);
 int dsm_tts_speaker_empty(dsm_tts*, float* ca_src_out, int cap_rows, int* rows_out);
+/* A request's text schedule on the device, K steps per visit — the inference loop of the reference's TTS worker
+ * (srv/tts.rs:574-621 with words arriving on a channel, :852-907 over a whole prompt) for B slots at once.  The word queue, the
+ * cursor (current word, token_idx, step_past_last_token, last_epad_index), last_text_token, consecutive_pads and the step index
+ * of every slot live in device memory; two one-thread-per-slot kernels around each step's groups pick `allowed` and
+ * prev_text_token and assemble the input tokens (core/tts_streaming.rs:126-158), then do the loop body behind State::step
+ * (srv/tts.rs:596-614).  dsm_tts_run only enqueues; dsm_tts_collect waits once for the whole block and replays its records into
+ * the host-side token tables, so dsm_tts_audio_tokens / dsm_tts_step_idx answer as after the same dsm_tts_step calls.
+ *   dsm_tts_request_begin       a fresh slot (step index 0: dsm_tts_reset_slot, then dsm_tts_set_ca_src / dsm_tts_set_sampling as
+ *     needed) starts a request: last_text_token = text_start_token, current word = the empty word (srv/tts.rs:577), so the
+ *     first `allowed` is PadOrEpad.  max_seq_len: the loop's `0..max_seq_len` (srv/tts.rs:580); extra_steps: Config::extra_steps
+ *     (srv/tts.rs:572,584) — a per-request argument because dsm_tts_config has no such field.  DSM_ERR_STATE: the slot is not
+ *     fresh, has a request already, or a block waits.  DSM_ERR_INVALID: max_seq_len < 1 or extra_steps < 0.
+ *   dsm_tts_request_push_words  in_tx.send(Some(word_tokens)) for n_words words: tokens back to back, word_len [n_words] (a word
+ *     may be empty).  The caller inserts the bos token into the first word (srv/tts.rs:484-493).  The queue holds max_steps +
+ *     acoustic_delay tokens and as many words per request (a request cannot consume more than it has steps).  A push that does
+ *     not fit, or one on a closed slot or a slot without a request: DSM_ERR_STATE, nothing changed.  The upload rides the model
+ *     stream: it is ordered with the blocks, also with one that waits to be collected.
+ *   dsm_tts_request_close       in_tx.send(None) (srv/tts.rs:470): after the last word's end-of-pad the slot runs the tail of
+ *     extra_steps + text_audio_delay_in_tokens Pad steps and is DONE.
+ *   dsm_tts_run                 n_steps (1..DSM_TTS_RUN_MAX) steps of every slot with a request; enqueue only: no synchronize, no
+ *     download.  Before each step a slot in DSM_TTS_REQ_WAITING (end-of-pad seen, next word not pushed, not closed) takes its next
+ *     word if one has arrived and sits the step out otherwise — the reference blocks a thread in in_rx.recv() there; then the
+ *     termination test: step_past_last_token > extra_steps + text_audio_delay_in_tokens (DONE), max_seq_len steps done or the step
+ *     that would reach the engine's "max step-idx" (DONE_LIMIT).  decode = 1 (needs dsm_tts_attach_mimi and an empty PCM queue)
+ *     also decodes the frame every step completes, with dsm_tts_step_pcm's predicate, each step into a frame buffer and a pinned
+ *     PCM entry of its own.  DSM_ERR_STATE, nothing touched: a block waits for dsm_tts_collect; n_steps out of range; decode
+ *     without a Mimi.  While a block waits, dsm_tts_step / dsm_tts_step_pcm / dsm_tts_reset_slot return DSM_ERR_STATE; between
+ *     blocks dsm_tts_step* serves the other slots (mask[b] = 1 on a slot with a request: DSM_ERR_STATE).
+ *   dsm_tts_collect             waits for the block and fills `out` (every array is the caller's, sized for the n_steps given to
+ *     dsm_tts_run; any may be NULL).  A slot's text_token / audio entries are defined where stepped is 1 (audio: this step's
+ *     last_audio_tokens, or DSM_TTS_UNGENERATED below text_audio_delay_in_tokens).  Word events (srv/tts.rs:596-604) carry steps,
+ *     not text: word = push-order index (-1: the initial empty word), start_step = last_epad_index, stop_step = the slot's step
+ *     index before the step; seconds = step / 12.5.  n_events counts all of them, the first events_cap are stored.
+ *     overwrite_last_text_token(pad) (srv/tts.rs:609) is applied to the host's text-token table only; the token handed to the
+ *     next step stays the end-of-pad.  DSM_ERR_STATE when no block waits.
+ *   dsm_tts_request_status      DSM_TTS_REQ_* as of the last collect (RUNNING right after begin).  dsm_tts_reset_slot ends a
+ *     request: the slot is IDLE again. */
+#define DSM_TTS_RUN_MAX 16 /* steps per block: one frame buffer and one pinned PCM entry each (16 * B * 1920 * 4 bytes: 3.9 MB at B = 32) */
+enum { DSM_TTS_REQ_IDLE = 0, DSM_TTS_REQ_RUNNING = 1, DSM_TTS_REQ_WAITING = 2, DSM_TTS_REQ_DONE = 3, DSM_TTS_REQ_DONE_LIMIT = 4 };
+typedef struct dsm_tts_word_event { int slot, word, start_step, stop_step; } dsm_tts_word_event;
+typedef struct dsm_tts_block {
+  int n_steps;              /* out: steps of the block */
+  uint8_t* stepped;         /* [n][B] the slot took this step */
+  uint32_t* text_token;     /* [n][B] */
+  uint32_t* audio;          /* [n][B][num_slices] */
+  float* pcm;               /* [n][B][1920] or NULL; written where pcm_valid is 1 */
+  uint8_t* pcm_valid;       /* [n][B] or NULL */
+  dsm_tts_word_event* events;
+  int events_cap, n_events; /* in, out */
+  int* status;              /* [B] DSM_TTS_REQ_* after the block */
+} dsm_tts_block;
+int dsm_tts_request_begin(dsm_tts*, int slot, int max_seq_len, int extra_steps);
+int dsm_tts_request_push_words(dsm_tts*, int slot, const uint32_t* tokens, const int* word_len, int n_words);
+int dsm_tts_request_close(dsm_tts*, int slot);
+int dsm_tts_run(dsm_tts*, int n_steps, int decode);
+int dsm_tts_collect(dsm_tts*, dsm_tts_block* out);
+int dsm_tts_request_status(dsm_tts*, int slot);
 int dsm_tts_debug_read(dsm_tts*, const char* name, float* out, size_t cap); /* "lm.hidden", "lm.logits": one row per BATCH ROW (2 per slot with cfg_rows) */
 int dsm_tts_get_metrics(dsm_tts*, dsm_metrics* out); /* graph_launches / eager_bodies only */
 
