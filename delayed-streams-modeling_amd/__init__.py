@@ -137,7 +137,10 @@ ABI_SYMBOLS = [
     "dsm_tts_attach_speaker_encoder", "dsm_tts_encode_voice", "dsm_tts_speaker_empty",
     "dsm_tts_request_begin", "dsm_tts_request_push_words", "dsm_tts_request_close", "dsm_tts_run", "dsm_tts_collect",
     "dsm_tts_request_status",
+    "dsm_tts_attach_conditioners", "dsm_tts_set_condition_lut", "dsm_tts_set_condition_cont", "dsm_tts_set_condition_padding",
+    "dsm_tts_clear_condition",
 ]
+TTS_COND_LUT, TTS_COND_CONTINUOUS = 0, 1  # DSM_TTS_COND_*
 TTS_RUN_MAX = 16  # DSM_TTS_RUN_MAX
 TTS_REQ_IDLE, TTS_REQ_RUNNING, TTS_REQ_WAITING, TTS_REQ_DONE, TTS_REQ_DONE_LIMIT = range(5)  # DSM_TTS_REQ_*
 
@@ -152,6 +155,13 @@ class TtsBlockC(C.Structure):
     _fields_ = [("n_steps", C.c_int), ("stepped", C.c_void_p), ("text_token", C.c_void_p), ("audio", C.c_void_p),
                 ("pcm", C.c_void_p), ("pcm_valid", C.c_void_p), ("events", C.POINTER(TtsWordEvent)),
                 ("events_cap", C.c_int), ("n_events", C.c_int), ("status", C.c_void_p)]
+
+
+class TtsConditionerDesc(C.Structure):
+    """dsm_tts_conditioner_desc (include/dsm.h): one entry of [modules.<m>.model.conditioners]."""
+    _fields_ = [("name", C.c_char_p), ("type", C.c_int), ("dim", C.c_int), ("n_bins", C.c_int),
+                ("possible_values", C.POINTER(C.c_char_p)), ("n_values", C.c_int),
+                ("scale_factor", C.c_float), ("max_period", C.c_float)]
 
 
 TtsBlock = collections.namedtuple("TtsBlock", "n_steps stepped text_token audio pcm pcm_valid events status")
@@ -302,6 +312,11 @@ def load_library(path=None):
     lib.dsm_tts_run.argtypes = [vp, C.c_int, C.c_int]
     lib.dsm_tts_collect.argtypes = [vp, C.POINTER(TtsBlockC)]
     lib.dsm_tts_request_status.argtypes = [vp, C.c_int]
+    lib.dsm_tts_attach_conditioners.argtypes = [vp, C.POINTER(TtsConditionerDesc), C.c_int, C.c_char_p]
+    lib.dsm_tts_set_condition_lut.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p]
+    lib.dsm_tts_set_condition_cont.argtypes = [vp, C.c_int, C.c_char_p, C.c_float]
+    lib.dsm_tts_set_condition_padding.argtypes = [vp, C.c_int, C.c_char_p]
+    lib.dsm_tts_clear_condition.argtypes = [vp, C.c_int]
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
         getattr(lib, name).restype = C.c_int
@@ -1055,3 +1070,37 @@ class TtsEngine:
         u = None if ca_src_uncond is None else np.ascontiguousarray(ca_src_uncond, dtype=np.float32)
         self._check(self.lib.dsm_tts_set_ca_src(self.h, slot, _ptr(a), 0 if a is None else a.shape[0], _ptr(u),
                                                 0 if u is None else u.shape[0], float(cfg_alpha)))
+
+    # ---- conditioners (core/conditioner.rs): one Condition::AddToInput per slot ----
+    def attach_conditioners(self, descs, lm_path):
+        """ConditionProvider::new: descs as config_toml.load_tts_conditioners returns them — dicts with name, type ("Lut" /
+        "ContinuousAttribute"), dim and n_bins + possible_values or scale_factor + max_period; tensors from lm_path."""
+        arr = (TtsConditionerDesc * len(descs))()
+        keep = []  # the strings the array points to
+        for a, dsc in zip(arr, descs):
+            if dsc["type"] not in ("Lut", "ContinuousAttribute"):
+                raise ValueError(f"conditioner type {dsc['type']!r}")
+            name = dsc["name"].encode()
+            keep.append(name)
+            a.name, a.dim = name, int(dsc["dim"])
+            if dsc["type"] == "Lut":
+                vals = (C.c_char_p * len(dsc["possible_values"]))(*[v.encode() for v in dsc["possible_values"]])
+                keep.append(vals)
+                a.type, a.n_bins, a.possible_values, a.n_values = TTS_COND_LUT, int(dsc["n_bins"]), vals, len(vals)
+            else:
+                a.type, a.scale_factor, a.max_period = TTS_COND_CONTINUOUS, float(dsc["scale_factor"]), float(dsc["max_period"])
+        self._check(self.lib.dsm_tts_attach_conditioners(self.h, arr, len(descs), lm_path.encode()))
+
+    def set_condition(self, slot, name, value):
+        """condition_lut (value: str) or condition_cont (value: a number) on a fresh slot; replaces the slot's condition."""
+        if isinstance(value, str):
+            self._check(self.lib.dsm_tts_set_condition_lut(self.h, slot, name.encode(), value.encode()))
+        else:
+            self._check(self.lib.dsm_tts_set_condition_cont(self.h, slot, name.encode(), float(value)))
+
+    def set_condition_padding(self, slot, name):
+        """The conditioner's learnt_padding as the slot's condition."""
+        self._check(self.lib.dsm_tts_set_condition_padding(self.h, slot, name.encode()))
+
+    def clear_condition(self, slot):
+        self._check(self.lib.dsm_tts_clear_condition(self.h, slot))

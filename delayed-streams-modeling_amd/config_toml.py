@@ -52,6 +52,60 @@ def _transformer(t, dst):
         raise ConfigError("cross_attention (TTS speaker conditioning) is outside the STT path")
 
 
+def load_tts_conditioners(path, module=None):
+    """The `[modules.<m>.model.conditioners.*]` tables of a moshi-server toml (conditioner::Config, core/conditioner.rs:8-29) as
+    the descriptor list TtsEngine.attach_conditioners takes, in file order: dicts with name, type and dim, plus n_bins and
+    possible_values ("Lut") or scale_factor and max_period ("ContinuousAttribute").  [] when the module defines none."""
+    with open(path, "rb") as f:
+        doc = tomli.load(f)
+    mods = doc.get("modules", {})
+    cands = {k: v for k, v in mods.items() if isinstance(v, dict) and v.get("type") == "Tts"}
+    if module is not None:
+        cands = {module: cands[module]} if module in cands else {}
+    if len(cands) != 1:
+        raise ConfigError(f"expected exactly one Tts module, found {sorted(cands)}")
+    name, m = next(iter(cands.items()))
+    model = m.get("model")
+    if not isinstance(model, dict):
+        raise ConfigError("modules.%s.model is required" % name)
+    tables = model.get("conditioners", {})
+    if not isinstance(tables, dict):
+        raise ConfigError("modules.%s.model.conditioners must be a table of tables" % name)
+    out = []
+    for cname, c in tables.items():
+        where = f"conditioners.{cname}"
+        if not isinstance(c, dict):
+            raise ConfigError(f"{where} must be a table")
+        kind = c.get("type")
+        if kind not in ("Lut", "ContinuousAttribute"):
+            raise ConfigError(f"{where}.type {kind!r}: Lut or ContinuousAttribute")
+        dim = c.get("dim")
+        if not isinstance(dim, int) or isinstance(dim, bool) or dim < 1:
+            raise ConfigError(f"{where}.dim must be a positive integer")
+        d = dict(name=cname, type=kind, dim=dim)
+        if kind == "Lut":
+            n_bins, vals = c.get("n_bins"), c.get("possible_values")
+            if not isinstance(n_bins, int) or isinstance(n_bins, bool) or n_bins < 0:
+                raise ConfigError(f"{where}.n_bins must be a non-negative integer")
+            if not isinstance(vals, list) or not vals or not all(isinstance(v, str) for v in vals):
+                raise ConfigError(f"{where}.possible_values must be a non-empty list of strings")
+            if len(vals) > n_bins + 1:
+                raise ConfigError(f"{where}: {len(vals)} possible_values for an embedding of n_bins + 1 = {n_bins + 1} rows")
+            d.update(n_bins=n_bins, possible_values=list(vals))
+        else:
+            for k in ("scale_factor", "max_period"):
+                v = c.get(k)
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    raise ConfigError(f"{where}.{k} must be a number")
+                d[k] = float(v)
+            if dim < 4 or dim % 2:
+                raise ConfigError(f"{where}.dim {dim}: a continuous attribute needs an even dim of at least 4")
+            if not d["max_period"] > 0:
+                raise ConfigError(f"{where}.max_period must be positive")
+        out.append(d)
+    return out
+
+
 def load_batched_asr(path, module=None):
     """Returns (AsrConfig, host) for the BatchedAsr module of a moshi-server toml.
     host = {batch_size, lm_model_file, audio_tokenizer_file, text_tokenizer_file, path, instance_name, ...}."""

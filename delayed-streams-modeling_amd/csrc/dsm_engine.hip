@@ -1099,5 +1099,6 @@ int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, 
 #include "dsm_tts.inc"
 #include "dsm_tts_request.inc"
 #include "dsm_speaker.inc"
+#include "dsm_tts_cond.inc"
 #include "dsm_audio.inc"
 #include "dsm_worker.inc"

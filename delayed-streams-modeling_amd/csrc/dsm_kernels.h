@@ -1633,10 +1633,16 @@ __global__ void lm_gumbel_kernel(const float* __restrict__ logits, int V, float 
 // ------------------------------------------------------------------------------------------
 // TTS glue — core/tts_streaming.rs:117-242, core/lm.rs:640-684, :983-995
 // ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float dsm_unpaired(float v);  // below, with the SEANet front end that first needed it
+
 // tokens [B][1+nc] int32: text token, then one entry per codebook; -1 = None ("literal zeros": the embedding is skipped)
-__global__ void tts_input_kernel(float* __restrict__ x, const uint16_t* __restrict__ text_emb,
+// x, xin ("lm.input": x is overwritten by the layers) and tokens start at the group's first row r0.  cond [slots][d] / cond_on
+// [slots] are the whole batch's: a slot whose flag is set adds its Condition::AddToInput row last, to every row it owns
+// (emb.broadcast_add(v), core/lm.rs:996-1000,1062-1066).  Behind the flag, never a zero row: x + 0.0f would turn -0.0f into +0.0f.
+__global__ void tts_input_kernel(float* __restrict__ x, float* __restrict__ xin, const uint16_t* __restrict__ text_emb,
                                  const uint16_t* __restrict__ audio_emb /* [nc][audio_vocab][d] */,
-                                 const int32_t* __restrict__ tokens, int nc, int d, int audio_vocab) {
+                                 const int32_t* __restrict__ tokens, int nc, int d, int audio_vocab,
+                                 const float* __restrict__ cond, const uint8_t* __restrict__ cond_on, int r0, int rps) {
   const int b = blockIdx.x;
   __shared__ int32_t toks[72];
   if ((int)threadIdx.x < 1 + nc) toks[threadIdx.x] = tokens[b * (1 + nc) + threadIdx.x];
@@ -1652,8 +1658,35 @@ __global__ void tts_input_kernel(float* __restrict__ x, const uint16_t* __restri
       e0 = e0 + __uint_as_float(a2 << 16);
       e1 = e1 + __uint_as_float(a2 & 0xFFFF0000u);
     }
+    const int slot = (r0 + b) / rps;
+    if (cond_on[slot]) {
+      const float2 c = *reinterpret_cast<const float2*>(cond + (long)slot * d + j);
+      e0 = dsm_unpaired(e0 + c.x);  // two scalar adds, not a v_pk_add_f32
+      e1 = dsm_unpaired(e1 + c.y);
+    }
     *reinterpret_cast<float2*>(x + (long)b * d + j) = make_float2(e0, e1);
+    *reinterpret_cast<float2*>(xin + (long)b * d + j) = make_float2(e0, e1);
   }
+}
+
+// One slot's Condition::AddToInput row (core/conditioner.rs:50-58 condition_lut, :102-110 condition_cont, :168-175 learnt_padding):
+// row[j] = sum_k in[k] * W[j][k], ONE f32 fma chain per output element over k = 0 .. dim - 1 ascending, starting from 0.
+// in [dim]: the LUT's embedding row, or the sin embedding already rounded to bf16; W [d][dim] = output_proj.weight.
+// W == nullptr: row = in [d] (learnt_padding).  Sets the slot's flag behind the row; one launch per dsm_tts_set_condition_* call.
+__global__ void tts_cond_row_kernel(float* __restrict__ row, uint8_t* __restrict__ on, const float* __restrict__ in,
+                                    const float* __restrict__ W, int d, int dim) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < d) {
+    float acc = 0.0f;
+    if (W) {
+      const float* w = W + (long)j * dim;
+      for (int k = 0; k < dim; ++k) acc = __builtin_fmaf(in[k], w[k], acc);
+    } else {
+      acc = in[j];
+    }
+    row[j] = acc;
+  }
+  if (j == 0) *on = 1;
 }
 
 // Seeded top-k sampling of one row by a 256-thread block (dsm_sampling.h: LogitsProcessor with Sampling::TopK).

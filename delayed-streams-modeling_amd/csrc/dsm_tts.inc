@@ -39,6 +39,20 @@ struct SpkEnc {
   float last_ms = 0.0f;
 };
 
+// ConditionProvider (core/conditioner.rs:119-176) once dsm_tts_attach_conditioners has loaded it (dsm_tts_cond.inc).  Every tensor
+// is kept as f32 (the upcast of a BF16 checkpoint is exact).
+struct TtsCond {
+  struct One {
+    std::string name;
+    int type = 0, dim = 0;
+    std::vector<std::string> values;  // LUT: value -> its position
+    float scale_factor = 0.0f, max_period = 0.0f;
+    float *embed = nullptr, *proj = nullptr, *pad = nullptr;  // [n_bins + 1][dim] (LUT), [d_model][dim], [d_model]
+  };
+  std::vector<One> list;
+  float* d_in = nullptr;  // [largest dim] staging of a continuous conditioner's sin embedding
+};
+
 }  // namespace
 
 struct dsm_tts : DsmDevice {
@@ -115,6 +129,13 @@ struct dsm_tts : DsmDevice {
   uint64_t pcm_seq = 0;  // step_pcm calls so far: entry / frame buffer of call n is n & 1
   int pcm_pending = 0;   // entries queued and not yet delivered (the oldest is (pcm_seq - pcm_pending) & 1)
   SpkEnc spk;            // voice clips -> cross-attention rows (dsm_tts_attach_speaker_encoder, dsm_speaker.inc)
+  // ---- per-slot Condition::AddToInput (dsm_tts_cond.inc) ----
+  // Allocated at create and never moved: tts_input_kernel of every captured step body reads these two, so a condition set after
+  // capture is seen on replay.  lm_in [R][d_model] keeps the rows that kernel wrote ("lm.input").
+  TtsCond cond;
+  float *d_cond = nullptr, *lm_in = nullptr;  // [B][d_model] f32, zero where no condition is set
+  uint8_t* d_cond_on = nullptr;               // [B]
+  std::vector<uint8_t> cond_on;               // host mirror
   // ---- a request's text schedule on the device, K steps per visit (dsm_tts_request.inc) ----
   // Frames of a block: every step of a block fills a frame buffer and a pinned PCM entry of its own (buffers 3 .. 3 +
   // DSM_TTS_RUN_MAX - 1 of d_fcodes / d_fvalid, blk_pcm[s]) — no event wait holds the model stream back for the decode stream.
@@ -403,6 +424,11 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
     if ((rc = e->halloc(&t->h_ca_has, (size_t)R))) return rc;
     t->reqs.assign(B, dsm_tts::ReqHost{});
   }
+  // the conditioners' buffers (dsm_tts_cond.inc), behind every other allocation
+  if ((rc = e->dalloc(&t->lm_in, (size_t)R * d))) return rc;
+  if ((rc = e->dalloc(&t->d_cond, (size_t)B * d))) return rc;
+  if ((rc = e->dalloc(&t->d_cond_on, B))) return rc;
+  t->cond_on.assign(B, 0);
   t->items.resize(B);
   for (auto& it : t->items) {
     it.audio_tokens.assign(t->n_steps * S, DSM_TTS_UNGENERATED);
@@ -522,8 +548,8 @@ int tts_group_body(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp, bool run_dep) 
   const CaState* ca = c.cross_attention ? &grp.ca : nullptr;
   e->tag_gemm[sid] = DSM_PROF_GEMM_LM;
   e->tag_attn[sid] = DSM_PROF_ATTN_LM;
-  hipLaunchKernelGGL(tts_input_kernel, dim3(B, (d + 511) / 512), dim3(256), 0, st, sc.x, t->lm.text_emb, t->lm.audio_emb,
-                     t->d_tokens + (size_t)r0 * (1 + nc), nc, d, c.audio_vocab_size);
+  hipLaunchKernelGGL(tts_input_kernel, dim3(B, (d + 511) / 512), dim3(256), 0, st, sc.x, t->lm_in + (size_t)r0 * d, t->lm.text_emb,
+                     t->lm.audio_emb, t->d_tokens + (size_t)r0 * (1 + nc), nc, d, c.audio_vocab_size, t->d_cond, t->d_cond_on, r0, rps);
   HIPCHK(hipGetLastError());
   int rc = with_kv_type(c.kv_bf16 != 0, [&](auto kv) {  // forward_cond, or forward_ca for rows that carry a source (core/lm.rs:957-1067)
     return transformer_forward<uint16_t, decltype(kv)>(e, st, t->lm.tr, grp.tr, sc, B, 1, t->d_rmask + r0, nullptr, plain_map(1, 1),
@@ -982,6 +1008,8 @@ int dsm_tts_reset_slot(dsm_tts* t, int slot) {
     if (int rc = dsm_tts_set_sampling(t, slot, 0, 0.0f, 0)) return rc;
   if (t->cfg.cross_attention)  // ... and whatever ca_src / cfg_alpha its creator passes: none until dsm_tts_set_ca_src
     if (int rc = dsm_tts_set_ca_src(t, slot, nullptr, 0, nullptr, 0, 0.0)) return rc;
+  if (t->cond_on[slot])  // ... and no Condition until dsm_tts_set_condition_*
+    if (int rc = dsm_tts_clear_condition(t, slot)) return rc;
   DsmDevice* e = t;
   dsm_tts::Item& it = t->items[slot];
   it.step_idx = 0;
@@ -1011,6 +1039,8 @@ int dsm_tts_debug_read(dsm_tts* t, const char* name, float* out, size_t cap) {
   if (!strcmp(name, "lm.hidden")) { src = t->hidden; n = (size_t)t->R * t->cfg.lm.d_model; }
   else if (!strcmp(name, "lm.logits")) { src = t->logits; n = (size_t)t->R * t->cfg.text_out_vocab_size; }
   else if (!strcmp(name, "dep.logits")) { src = t->dlogits; n = (size_t)t->R * (t->cfg.audio_vocab_size - 1); }
+  else if (!strcmp(name, "lm.input")) { src = t->lm_in; n = (size_t)t->R * t->cfg.lm.d_model; }  // the rows tts_input_kernel wrote in the last step
+  else if (!strcmp(name, "cond.row")) { src = t->d_cond; n = (size_t)t->B * t->cfg.lm.d_model; }  // [B][d_model], zeros without a condition
   if (!src) return DSM_ERR_INVALID;
   if (n > cap) n = cap;
   HIPCHK(hipSetDevice(e->device));

@@ -152,11 +152,13 @@ def lm_spec(cfg):
     return s
 
 
-def tts_spec(cfg, legacy_ca=False, speaker=False, mimi_dim=0):
+def tts_spec(cfg, legacy_ca=False, speaker=False, mimi_dim=0, conditioners=None):
     """TTS checkpoint keys (core/lm.rs:501-590): main LM + shared depformer with per-group gating/linear_in.
     cfg.cross_attention adds every layer's norm_cross + cross_attention tensors (legacy_ca: the single in_proj_weight layout).
     speaker: the two SpeakerEncoder tensors (core/tts_streaming.rs:353-362) for a speaker tokenizer of width mimi_dim, appended
-    (every tensor has its own stream, so the other tensors' bytes do not change)."""
+    (every tensor has its own stream, so the other tensors' bytes do not change).
+    conditioners: descriptors as config_toml.load_tts_conditioners returns them; appends each one's embed.weight (Lut),
+    output_proj.weight and learnt_padding (core/conditioner.rs:41-47,74-76)."""
     s = Spec()
     t, dp = cfg.lm, cfg.depformer
     d, D, S, G, lr = t.d_model, dp.d_model, cfg.dep_num_slices, cfg.dep_weight_groups, cfg.dep_low_rank
@@ -208,18 +210,32 @@ def tts_spec(cfg, legacy_ca=False, speaker=False, mimi_dim=0):
         p = "condition_provider.conditioners.speaker_wavs"
         s.add(f"{p}.output_proj.weight", (cond, mimi_dim), "normal", mimi_dim ** -0.5)
         s.add(f"{p}.learnt_padding", (1, 1, cond), "normal", 0.5)
+    for c in conditioners or []:
+        p = f"condition_provider.conditioners.{c['name']}"
+        if c["type"] == "Lut":
+            s.add(f"{p}.embed.weight", (c["n_bins"] + 1, c["dim"]), "normal", 1.0)
+        s.add(f"{p}.output_proj.weight", (d, c["dim"]), "normal", c["dim"] ** -0.5)
+        s.add(f"{p}.learnt_padding", (1, 1, d), "normal", 0.5)
     return s
 
 
-def make_synth_tts_weights(cfg, out_dir, seed=SEED, tag="tts", legacy_ca=False, speaker=False, mimi_dim=0):
+def conditioners_tag(conditioners):
+    """The file-name suffix that tells sets of conditioners apart: _cond-<name>.<dim>[.<n_bins>]..."""
+    return "_cond" + "".join("-%s.%d" % (c["name"], c["dim"]) + (".%d" % c["n_bins"] if c["type"] == "Lut" else "") for c in conditioners)
+
+
+def make_synth_tts_weights(cfg, out_dir, seed=SEED, tag="tts", legacy_ca=False, speaker=False, mimi_dim=0, conditioners=None):
     """The tag must tell configurations apart (files are cached by name): use e.g. "tts_tiny_ca" with cfg.cross_attention.
-    speaker=True (with the speaker tokenizer's mimi_dim) adds the SpeakerEncoder tensors; the file is <tag>_spk<mimi_dim>."""
+    speaker=True (with the speaker tokenizer's mimi_dim) adds the SpeakerEncoder tensors; the file is <tag>_spk<mimi_dim>.
+    conditioners=[...] adds the condition provider's tensors; the file name gains conditioners_tag(conditioners)."""
     os.makedirs(out_dir, exist_ok=True)
     if speaker:
         tag = f"{tag}_spk{mimi_dim}"
+    if conditioners:
+        tag += conditioners_tag(conditioners)
     path = os.path.join(out_dir, f"{tag}.lm.safetensors")
     if not os.path.exists(path):
-        write_safetensors(path, tts_spec(cfg, legacy_ca, speaker, mimi_dim), "BF16", seed)
+        write_safetensors(path, tts_spec(cfg, legacy_ca, speaker, mimi_dim, conditioners), "BF16", seed)
     return path
 
 

@@ -477,7 +477,39 @@ int dsm_tts_request_close(dsm_tts*, int slot);
 int dsm_tts_run(dsm_tts*, int n_steps, int decode);
 int dsm_tts_collect(dsm_tts*, dsm_tts_block* out);
 int dsm_tts_request_status(dsm_tts*, int slot);
-int dsm_tts_debug_read(dsm_tts*, const char* name, float* out, size_t cap); /* "lm.hidden", "lm.logits": one row per BATCH ROW (2 per slot with cfg_rows) */
+/* Conditioners — ConditionProvider (core/conditioner.rs:31-176).  The reference's server builds one Condition::AddToInput per
+ * request (srv/tts.rs:416-423: condition_lut) and hands it to every State::step; LmModel::forward_cond / forward_ca add it to the
+ * input embedding sum of every batch row (core/lm.rs:996-1000, :1062-1066).  Here a slot carries at most one condition: its row
+ * [d_model] is computed on the device when it is set (one f32 fma chain per element over k ascending; a continuous value's sin
+ * embedding is rounded to bf16 first, like the reference's to_dtype) and is added last in the step's input sum, to both rows of
+ * a slot with cfg_rows.  The row stays f32: the reference's final rounding of the projected row to the checkpoint dtype is NOT
+ * applied, as for the speaker rows.  A slot without a condition computes exactly what an engine without conditioners computes.
+ *   dsm_tts_attach_conditioners    ConditionProvider::new.  Reads condition_provider.conditioners.<name>.{embed.weight
+ *     [n_bins + 1][dim] (LUT only), output_proj.weight [d_model][dim], learnt_padding [1,1,d_model]} (BF16 or F32, kept as f32)
+ *     from lm_safetensors.  Once per engine, at any time (captured graphs stay valid).  DSM_ERR_IO for a missing key or a wrong
+ *     shape (the engine is left as it was), DSM_ERR_INVALID for a bad descriptor, DSM_ERR_STATE when attached already.
+ *   dsm_tts_set_condition_lut / _cont / _padding   condition_lut, condition_cont, learnt_padding; a later call replaces the
+ *     slot's condition.  Only on a fresh slot (step index 0, no block waiting), like dsm_tts_set_ca_src: DSM_ERR_STATE otherwise,
+ *     nothing touched.  DSM_ERR_INVALID: no conditioners attached, an unknown name, a LUT value that is not listed, a string for
+ *     a continuous conditioner or a number for a LUT.  A condition set before dsm_tts_request_begin applies to the request.
+ *   dsm_tts_clear_condition        always allowed; dsm_tts_reset_slot clears too (a fresh State).
+ * dsm_tts_debug_read taps: "cond.row" [B][d_model] (zeros for a slot without a condition), "lm.input" [rows][d_model]: the
+ * input sums of the last step. */
+enum { DSM_TTS_COND_LUT = 0, DSM_TTS_COND_CONTINUOUS = 1 };
+typedef struct dsm_tts_conditioner_desc {
+  const char* name;                     /* key under condition_provider.conditioners. */
+  int type, dim;
+  int n_bins;                           /* LUT: embed.weight is [n_bins + 1][dim] */
+  const char* const* possible_values;   /* LUT: value -> its position in this list */
+  int n_values;
+  float scale_factor, max_period;       /* continuous */
+} dsm_tts_conditioner_desc;
+int dsm_tts_attach_conditioners(dsm_tts*, const dsm_tts_conditioner_desc*, int n, const char* lm_safetensors);
+int dsm_tts_set_condition_lut(dsm_tts*, int slot, const char* name, const char* value);   /* condition_lut */
+int dsm_tts_set_condition_cont(dsm_tts*, int slot, const char* name, float value);        /* condition_cont */
+int dsm_tts_set_condition_padding(dsm_tts*, int slot, const char* name);                  /* learnt_padding */
+int dsm_tts_clear_condition(dsm_tts*, int slot);
+int dsm_tts_debug_read(dsm_tts*, const char* name, float* out, size_t cap); /* "lm.hidden", "lm.logits", "lm.input": one row per BATCH ROW (2 per slot with cfg_rows) */
 int dsm_tts_get_metrics(dsm_tts*, dsm_metrics* out); /* graph_launches / eager_bodies only */
 
 /* The LM step splits the batch into stream groups (slots [first, first+n) each on its own HIP stream) so that one
