@@ -101,7 +101,7 @@ class WorkerBackend(C.Structure):
     _fields_ = [("self", C.c_void_p), ("batch_size", C.c_int), ("asr_delay_in_tokens", C.c_int),
                 ("extra_heads_num", C.c_int), ("encode_step", BE_ENCODE), ("reset_slot", BE_RESET),
                 ("step_tokens", BE_STEP), ("poll_msgs", BE_POLL), ("last_error", BE_ERROR),
-                ("encode_async", BE_ENCODE_ASYNC), ("step_ticket", BE_STEP_TICKET)]
+                ("encode_async", BE_ENCODE_ASYNC), ("step_ticket", BE_STEP_TICKET), ("text_out_vocab_size", C.c_int)]
 
 
 class Metrics(C.Structure):
@@ -139,6 +139,9 @@ ABI_SYMBOLS = [
     "dsm_tts_request_status",
     "dsm_tts_attach_conditioners", "dsm_tts_set_condition_lut", "dsm_tts_set_condition_cont", "dsm_tts_set_condition_padding",
     "dsm_tts_clear_condition",
+    "dsm_spm_load", "dsm_spm_load_bytes", "dsm_spm_free", "dsm_spm_last_error", "dsm_spm_vocab_size", "dsm_spm_special_ids",
+    "dsm_spm_encode", "dsm_spm_decode", "dsm_worker_set_tokenizer_file",
+    "dsm_tts_attach_tokenizer", "dsm_tts_request_push_text", "dsm_tts_word_text",
 ]
 TTS_COND_LUT, TTS_COND_CONTINUOUS = 0, 1  # DSM_TTS_COND_*
 TTS_RUN_MAX = 16  # DSM_TTS_RUN_MAX
@@ -317,6 +320,23 @@ def load_library(path=None):
     lib.dsm_tts_set_condition_cont.argtypes = [vp, C.c_int, C.c_char_p, C.c_float]
     lib.dsm_tts_set_condition_padding.argtypes = [vp, C.c_int, C.c_char_p]
     lib.dsm_tts_clear_condition.argtypes = [vp, C.c_int]
+    lib.dsm_spm_load.argtypes = [C.c_char_p, C.POINTER(vp)]
+    lib.dsm_spm_load_bytes.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp)]
+    lib.dsm_spm_free.argtypes = [vp]
+    lib.dsm_spm_free.restype = None
+    lib.dsm_spm_last_error.argtypes = [vp]
+    lib.dsm_spm_last_error.restype = C.c_char_p
+    lib.dsm_spm_vocab_size.argtypes = [vp]
+    lib.dsm_spm_special_ids.argtypes = [vp] + [C.POINTER(C.c_int)] * 4
+    lib.dsm_spm_encode.argtypes = [vp, C.c_char_p, C.c_size_t, u32p, C.c_size_t]
+    lib.dsm_spm_encode.restype = C.c_int64
+    lib.dsm_spm_decode.argtypes = [vp, u32p, C.c_size_t, vp, C.c_size_t]
+    lib.dsm_spm_decode.restype = C.c_int64
+    lib.dsm_worker_set_tokenizer_file.argtypes = [vp, C.c_char_p]
+    lib.dsm_tts_attach_tokenizer.argtypes = [vp, C.c_char_p]
+    lib.dsm_tts_request_push_text.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]
+    lib.dsm_tts_word_text.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
+    lib.dsm_tts_word_text.restype = C.c_int64
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
         getattr(lib, name).restype = C.c_int
@@ -501,13 +521,76 @@ def decode_out_msg(raw):
     return out
 
 
+class Tokenizer:
+    """The native SentencePiece tokenizer (dsm_spm_*, csrc/dsm_spm.h): a UNIGRAM model from a path or from the file's bytes.
+    encode / decode answer byte for byte what sentencepiece.SentencePieceProcessor does with the same file; text crosses as
+    UTF-8 bytes (a str is encoded first), decode returns bytes."""
+
+    def __init__(self, model):
+        self.lib = load_library()
+        h = C.c_void_p()
+        if isinstance(model, (bytes, bytearray, memoryview)):
+            raw = bytes(model)
+            rc = self.lib.dsm_spm_load_bytes(raw, len(raw), C.byref(h))
+        else:
+            rc = self.lib.dsm_spm_load(os.fsencode(model), C.byref(h))
+        if rc != 0:
+            e = DsmError(f"dsm error {rc}: {self.lib.dsm_spm_last_error(None).decode(errors='replace')}")
+            e.code = rc
+            raise e
+        self.h = h
+
+    @property
+    def vocab_size(self):
+        return self.lib.dsm_spm_vocab_size(self.h)
+
+    @property
+    def special_ids(self):
+        """(unk, bos, eos, pad); -1 where the model has none."""
+        v = [C.c_int(-1) for _ in range(4)]
+        self.lib.dsm_spm_special_ids(self.h, *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def encode(self, text):
+        raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        ids = np.zeros(max(8, 2 * len(raw) + 8), dtype=np.uint32)
+        n = self.lib.dsm_spm_encode(self.h, raw, len(raw), _ptr(ids), ids.size)
+        if n > ids.size:  # the call wrote nothing: it tells the size
+            ids = np.zeros(n, dtype=np.uint32)
+            n = self.lib.dsm_spm_encode(self.h, raw, len(raw), _ptr(ids), ids.size)
+        return [int(x) for x in ids[:n]]
+
+    def decode(self, ids):
+        a = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        n = self.lib.dsm_spm_decode(self.h, _ptr(a) if a.size else None, a.size, None, 0)
+        if n < 0:
+            e = DsmError(f"dsm error {n}: {self.lib.dsm_spm_last_error(self.h).decode(errors='replace')}")
+            e.code = int(n)
+            raise e
+        out = C.create_string_buffer(max(1, n))
+        self.lib.dsm_spm_decode(self.h, _ptr(a) if a.size else None, a.size, out, n)
+        return out.raw[:n]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.dsm_spm_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Worker:
     """moshi-server's BatchedAsr module above an AsrEngine, minus the sockets: slot table, per-channel PCM queue,
     markers, message fan-out (srv/batched_asr.rs).  Messages cross this interface as the msgpack bytes of the wire."""
 
-    def __init__(self, engine=None, detokenizer=None, backend=None):
+    def __init__(self, engine=None, detokenizer=None, backend=None, tokenizer_file=None):
         """engine: an AsrEngine (the product path).  backend: a filled WorkerBackend instead (the tests drive the
-        worker logic with the CPU oracle through it); the caller keeps its callbacks alive."""
+        worker logic with the CPU oracle through it); the caller keeps its callbacks alive.  tokenizer_file: a SentencePiece
+        model for Word.text (dsm_worker_set_tokenizer_file); a detokenizer callback, if given too, wins."""
         self.lib, self.engine, self.backend = load_library(), engine, backend
         h = C.c_void_p()
         if backend is not None:
@@ -527,6 +610,15 @@ class Worker:
                 return len(s)
             self._cb = DETOK_FN(cb)
             self.lib.dsm_worker_set_detokenizer(self.h, self._cb, None)
+        if tokenizer_file is not None:
+            self.set_tokenizer_file(tokenizer_file)
+
+    def set_tokenizer_file(self, path):
+        rc = self.lib.dsm_worker_set_tokenizer_file(self.h, os.fsencode(path))
+        if rc < 0:
+            e = DsmError(f"dsm error {rc}: {self._err()}")
+            e.code = rc
+            raise e
 
     def _err(self):
         return self.lib.dsm_worker_last_error(self.h).decode()
@@ -1030,6 +1122,25 @@ class TtsEngine:
         lens = np.array([len(w) for w in words], dtype=np.int32)
         toks = np.array([t for w in words for t in w], dtype=np.uint32)
         self._check(self.lib.dsm_tts_request_push_words(self.h, slot, _ptr(toks) if toks.size else None, _ptr(lens), len(words)))
+
+    def attach_tokenizer(self, path):
+        """The SentencePiece model of push_text / word_text (the server's text_tokenizer); once per engine."""
+        self._check(self.lib.dsm_tts_attach_tokenizer(self.h, os.fsencode(path)))
+
+    def push_text(self, slot, text):
+        """One text message of the client (srv/tts.rs:480-494): split on spaces, each word encoded on its own, the bos in
+        front of the request's first word.  Returns the number of words queued; all or nothing."""
+        raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        n = C.c_int(0)
+        self._check(self.lib.dsm_tts_request_push_text(self.h, slot, raw, len(raw), C.byref(n)))
+        return n.value
+
+    def word_text(self, slot, word):
+        """WordWithTimestamps.text of word event `word` (-1: the initial empty word), as bytes."""
+        n = self._check(self.lib.dsm_tts_word_text(self.h, slot, word, None, 0))
+        out = C.create_string_buffer(max(1, n))
+        self._check(self.lib.dsm_tts_word_text(self.h, slot, word, out, n))
+        return out.raw[:n]
 
     def request_close(self, slot):
         """in_tx.send(None): no more words."""

@@ -28,6 +28,7 @@
 #include "dsm_kernels.h"
 #include "dsm_numerics.h"
 #include "dsm_safetensors.h"
+#include "dsm_spm.h"
 
 static thread_local std::string g_create_error;
 

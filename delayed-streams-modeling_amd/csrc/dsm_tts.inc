@@ -148,8 +148,10 @@ struct dsm_tts : DsmDevice {
     bool active = false, closed = false;
     int n_words = 0, n_tok = 0;
     int status = 0;  // DSM_TTS_REQ_* as of the last collect
+    bool bos_done = false;  // the request has received its first word (inserted_bos, srv/tts.rs:486-489)
   };
   std::vector<ReqHost> reqs;
+  std::unique_ptr<dsm_spm> tok;                    // dsm_tts_attach_tokenizer: text in (push_text), text out (word_text); host only
   int rec_ld = 0;                                  // TTS_REC_HDR + S
   int32_t *d_blk = nullptr, *h_blk = nullptr;      // [DSM_TTS_RUN_MAX][B][rec_ld] the block's records
   uint8_t *d_ca_has = nullptr, *h_ca_has = nullptr;  // [R] ca_len > 0, uploaded per block

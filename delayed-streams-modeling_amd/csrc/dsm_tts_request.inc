@@ -230,7 +230,70 @@ int dsm_tts_request_push_words(dsm_tts* t, int slot, const uint32_t* tokens, con
   HIPCHK(hipGetLastError());
   rq.n_tok += (int)n_tok;
   rq.n_words += n_words;
+  rq.bos_done = true;
   return 0;
+}
+
+int dsm_tts_attach_tokenizer(dsm_tts* t, const char* path) {
+  if (!t || !path) return DSM_ERR_INVALID;
+  DsmDevice* e = t;
+  if (t->tok) { e->set_error("a tokenizer is attached already"); return DSM_ERR_STATE; }
+  dsm_spm* tok = nullptr;
+  if (int rc = dsm_spm_load(path, &tok)) { e->set_error("tokenizer %s: %s", path, dsm_spm_last_error(nullptr)); return rc; }
+  if (dsm_spm_vocab_size(tok) > t->cfg.text_out_vocab_size) {
+    e->set_error("tokenizer %s has %d pieces, the model's text_out_vocab_size is %d", path, dsm_spm_vocab_size(tok), t->cfg.text_out_vocab_size);
+    dsm_spm_free(tok);
+    return DSM_ERR_INVALID;
+  }
+  t->tok.reset(tok);
+  return 0;
+}
+
+// recv_loop's body for one text message — srv/tts.rs:480-494.  Host work only: the words go through the upload of
+// dsm_tts_request_push_words, which checks everything before it touches the queue, so a refusal leaves the request as it was.
+int dsm_tts_request_push_text(dsm_tts* t, int slot, const char* utf8, size_t len, int* n_words_out) {
+  if (!t || slot < 0 || slot >= t->B || (!utf8 && len)) return DSM_ERR_INVALID;
+  DsmDevice* e = t;
+  if (!t->tok) { e->set_error("dsm_tts_request_push_text needs dsm_tts_attach_tokenizer first"); return DSM_ERR_STATE; }
+  const dsm_tts::ReqHost& rq = t->reqs[slot];
+  std::vector<uint32_t> tokens, ids;
+  std::vector<int> word_len;
+  for (size_t at = 0; at <= len;) {  // msg.split(' '): U+0020 only
+    size_t end = at;
+    while (end < len && utf8[end] != ' ') ++end;
+    if (end > at) {  // empty words are skipped; a word that normalizes to nothing is sent as an empty word, like upstream
+      dsm_spm_ns::encode(t->tok->m, (const uint8_t*)utf8 + at, end - at, ids);
+      const bool bos = !rq.bos_done && word_len.empty();  // inserted_bos
+      if (bos) tokens.push_back((uint32_t)t->cfg.text_bos_token);
+      tokens.insert(tokens.end(), ids.begin(), ids.end());
+      word_len.push_back((int)ids.size() + (bos ? 1 : 0));
+    }
+    at = end + 1;
+  }
+  if (n_words_out) *n_words_out = 0;
+  // zero words (a message of spaces) still goes through the checks: a slot that cannot take words refuses the message
+  if (int rc = dsm_tts_request_push_words(t, slot, tokens.data(), word_len.data(), (int)word_len.size())) return rc;
+  if (n_words_out) *n_words_out = (int)word_len.size();
+  return 0;
+}
+
+int64_t dsm_tts_word_text(dsm_tts* t, int slot, int word, char* out, size_t cap) {
+  if (!t || slot < 0 || slot >= t->B) return DSM_ERR_INVALID;
+  DsmDevice* e = t;
+  if (!t->tok) { e->set_error("dsm_tts_word_text needs dsm_tts_attach_tokenizer first"); return DSM_ERR_STATE; }
+  const dsm_tts::ReqHost& rq = t->reqs[slot];
+  if (!rq.active) { e->set_error("slot %d: no request (its word tokens are kept until dsm_tts_reset_slot)", slot); return DSM_ERR_STATE; }
+  if (word < -1 || word >= rq.n_words) { e->set_error("slot %d: no word %d (the request has received %d)", slot, word, rq.n_words); return DSM_ERR_INVALID; }
+  if (word == -1) return 0;  // Some(vec![]): the initial empty word — srv/tts.rs:577
+  const size_t q0 = (size_t)slot * t->qcap;
+  const int begin = word > 0 ? t->h_qend[q0 + word - 1] : 0, end = t->h_qend[q0 + word];
+  std::string text, err;
+  if (int rc = dsm_spm_ns::decode(t->tok->m, t->h_qtok + q0 + begin, (size_t)(end - begin), text, err)) {
+    e->set_error("slot %d word %d: %s", slot, word, err.c_str());
+    return rc;
+  }
+  if (out && text.size() <= cap && !text.empty()) memcpy(out, text.data(), text.size());
+  return (int64_t)text.size();
 }
 
 int dsm_tts_request_close(dsm_tts* t, int slot) {

@@ -15,6 +15,8 @@
 #include <memory>
 #include <queue>
 
+#include "dsm_spm.h"  // guarded: the library's translation unit has it already, the host-only harnesses get it here
+
 namespace {
 
 // ---- msgpack writer: the subset rmp_serde emits for these types (smallest integer form, f32/f64 as typed) ----
@@ -240,6 +242,7 @@ struct dsm_worker {
   std::deque<WPipelineMsg> pipe;      // encoder_loop -> model_loop (sync_channel, srv/batched_asr.rs:291)
   dsm_detok_fn detok = nullptr;
   void* detok_user = nullptr;
+  std::unique_ptr<dsm_spm> tok;  // dsm_worker_set_tokenizer_file: Word.text when no detok callback is set
   dsm_opus_decode_fn opus = nullptr;
   void* opus_user = nullptr;
   std::mutex mu;
@@ -380,6 +383,7 @@ int dsm_worker_create(dsm_engine* e, dsm_worker** out) {
   be.last_error = be_error;
   be.encode_async = be_encode_async;
   be.step_ticket = be_step_ticket;
+  be.text_out_vocab_size = e->cfg.text_out_vocab_size;
   return dsm_worker_create_with_backend(&be, out);
 }
 
@@ -409,6 +413,22 @@ void dsm_worker_set_detokenizer(dsm_worker* w, dsm_detok_fn fn, void* user) {
   std::lock_guard<std::mutex> lk(w->mu);
   w->detok = fn;
   w->detok_user = user;
+}
+
+int dsm_worker_set_tokenizer_file(dsm_worker* w, const char* path) {
+  if (!w || !path) return DSM_ERR_INVALID;
+  dsm_spm* tok = nullptr;
+  const int rc = dsm_spm_load(path, &tok);  // outside the lock: reading and indexing the file holds up no step
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (rc) { w->err = std::string("tokenizer ") + path + ": " + dsm_spm_last_error(nullptr); return rc; }
+  const int pieces = dsm_spm_vocab_size(tok), vocab = w->be.text_out_vocab_size;
+  if (vocab > 0 && pieces > vocab) {
+    w->err = std::string("tokenizer ") + path + " has " + std::to_string(pieces) + " pieces, the model's text_out_vocab_size is " + std::to_string(vocab);
+    dsm_spm_free(tok);
+    return DSM_ERR_INVALID;
+  }
+  w->tok.reset(tok);
+  return 0;
 }
 
 void dsm_worker_set_opus_decoder(dsm_worker* w, dsm_opus_decode_fn fn, void* user) {
@@ -705,7 +725,10 @@ int dsm_worker_step_model(dsm_worker* w) {
         int k = w->detok(w->detok_user, tk, am.n_tokens, tmp.data(), tmp.size());
         if (k < 0) { w->err = "detokenizer failed"; return DSM_ERR_STATE; }
         textbuf.assign(tmp.data(), (size_t)k);
-      } else {  // no sentencepiece model offline: the piece ids themselves
+      } else if (w->tok) {  // the native tokenizer; an id outside the model ends the step like the `?` at :667
+        std::string derr;
+        if (dsm_spm_ns::decode(w->tok->m, tk, (size_t)am.n_tokens, textbuf, derr)) { w->err = "Word of slot " + std::to_string(am.batch_idx) + ": " + derr; return DSM_ERR_STATE; }
+      } else {  // neither a callback nor a model: the piece ids themselves
         for (int j = 0; j < am.n_tokens; ++j) textbuf += (j ? " " : "") + std::to_string(tk[j]);
       }
       om.kind = DSM_OUT_WORD; om.text = textbuf.c_str(); om.time = am.time;

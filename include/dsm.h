@@ -450,8 +450,8 @@ int dsm_tts_speaker_empty(dsm_tts*, float* ca_src_out, int cap_rows, int* rows_o
  *     blocks dsm_tts_step* serves the other slots (mask[b] = 1 on a slot with a request: DSM_ERR_STATE).
  *   dsm_tts_collect             waits for the block and fills `out` (every array is the caller's, sized for the n_steps given to
  *     dsm_tts_run; any may be NULL).  A slot's text_token / audio entries are defined where stepped is 1 (audio: this step's
- *     last_audio_tokens, or DSM_TTS_UNGENERATED below text_audio_delay_in_tokens).  Word events (srv/tts.rs:596-604) carry steps,
- *     not text: word = push-order index (-1: the initial empty word), start_step = last_epad_index, stop_step = the slot's step
+ *     last_audio_tokens, or DSM_TTS_UNGENERATED below text_audio_delay_in_tokens).  Word events (srv/tts.rs:596-604) carry steps;
+ *     their text is dsm_tts_word_text: word = push-order index (-1: the initial empty word), start_step = last_epad_index, stop_step = the slot's step
  *     index before the step; seconds = step / 12.5.  n_events counts all of them, the first events_cap are stored.
  *     overwrite_last_text_token(pad) (srv/tts.rs:609) is applied to the host's text-token table only; the token handed to the
  *     next step stays the end-of-pad.  DSM_ERR_STATE when no block waits.
@@ -477,6 +477,23 @@ int dsm_tts_request_close(dsm_tts*, int slot);
 int dsm_tts_run(dsm_tts*, int n_steps, int decode);
 int dsm_tts_collect(dsm_tts*, dsm_tts_block* out);
 int dsm_tts_request_status(dsm_tts*, int slot);
+/* Text in, text out — the two ends of the request loop that the reference's server does with its text_tokenizer:
+ *   dsm_tts_attach_tokenizer    once after create.  DSM_ERR_IO / DSM_ERR_INVALID as dsm_spm_load; DSM_ERR_INVALID when the
+ *     model has more pieces than text_out_vocab_size; DSM_ERR_STATE when attached already.
+ *   dsm_tts_request_push_text   recv_loop's body for one text message (srv/tts.rs:480-494): split on U+0020 only, skip empty
+ *     words, encode each word on its own, text_bos_token in front of the first word the request receives — by this call or by
+ *     dsm_tts_request_push_words, whose caller inserts its own bos; "first" is per request (dsm_tts_request_begin resets it) —
+ *     then the queue upload of dsm_tts_request_push_words.  *n_words (may be NULL) = words queued.  All or nothing:
+ *     DSM_ERR_STATE with the queue and the first-word flag unchanged when the words do not fit, the slot is closed or has no
+ *     request, or no tokenizer is attached.
+ *   dsm_tts_word_text           WordWithTimestamps.text of word event `word` (srv/tts.rs:598): dsm_spm_decode of that word's
+ *     tokens as pushed, by either call (the bos decodes to nothing; word -1, the initial empty word, is "").  Returns the byte
+ *     length, and the needed one with nothing written when it exceeds cap.  The request's word tokens stay on the host until
+ *     dsm_tts_reset_slot; the queue's capacity bounds them.  DSM_ERR_STATE: no tokenizer, no request on the slot;
+ *     DSM_ERR_INVALID: no such word, or a pushed token outside the model. */
+int dsm_tts_attach_tokenizer(dsm_tts*, const char* path);
+int dsm_tts_request_push_text(dsm_tts*, int slot, const char* utf8, size_t len, int* n_words);
+int64_t dsm_tts_word_text(dsm_tts*, int slot, int word, char* out, size_t cap);
 /* Conditioners — ConditionProvider (core/conditioner.rs:31-176).  The reference's server builds one Condition::AddToInput per
  * request (srv/tts.rs:416-423: condition_lut) and hands it to every State::step; LmModel::forward_cond / forward_ca add it to the
  * input embedding sum of every batch row (core/lm.rs:996-1000, :1062-1066).  Here a slot carries at most one condition: its row
@@ -653,8 +670,34 @@ int dsm_inmsg_decode(const uint8_t* bytes, size_t len, dsm_in_msg* out, float* p
 int dsm_outmsg_decode(const uint8_t* bytes, size_t len, dsm_out_msg* out, char* text_buf, size_t text_cap,
                       float* prs_buf, size_t prs_cap);               /* client: protocol.rs decode_out_msg */
 
+/* ---- SentencePiece, native (csrc/dsm_spm.h; host only, no device work) ----
+ * The reference's servers hold a sentencepiece::SentencePieceProcessor: `text_tokenizer.encode(word)` in the TTS recv_loop
+ * (srv/tts.rs:485) and `decode_piece_ids` for every Word (srv/batched_asr.rs:667, srv/tts.rs:598).  These calls are that
+ * object for UNIGRAM models: the model file's normalizer (precompiled charsmap, whitespace rules, dummy prefix), the best
+ * unigram path with the module's own tie-breaks, byte fallback, and DecodeIds.  The model file is untrusted input: every
+ * length in it is checked and nothing of it is executed.
+ *   dsm_spm_load / dsm_spm_load_bytes   DSM_ERR_IO: unreadable, truncated or malformed.  DSM_ERR_INVALID: a well-formed model
+ *     outside the subset — BPE, WORD or CHAR model type, USER_DEFINED pieces, treat_whitespace_as_suffix, a denormalizer
+ *     charsmap (DESIGN.md says why).  dsm_spm_last_error(NULL) is the calling thread's message.
+ *   dsm_spm_special_ids   unk = the piece of type UNKNOWN; bos / eos / pad = trainer_spec's ids, -1 where that id is not a
+ *     CONTROL piece of the model (SentencePieceProcessor::bos_id() and friends answer the same).  Any pointer may be NULL.
+ *   dsm_spm_encode   SentencePieceProcessor::Encode(text) -> ids.  Returns the count; when it exceeds `cap` nothing is
+ *     written and the count says what is needed.  Malformed UTF-8 encodes as U+FFFD per byte, like the module.
+ *   dsm_spm_decode   DecodeIds: returns the byte length of the UTF-8 text (no NUL is written), same convention.  An id >=
+ *     dsm_spm_vocab_size is DSM_ERR_INVALID (dsm_spm_last_error(tok): the calling thread's message), not a skip.
+ * A loaded tokenizer is immutable: any number of threads may use it at once. */
+typedef struct dsm_spm dsm_spm;
+int dsm_spm_load(const char* path, dsm_spm** out);
+int dsm_spm_load_bytes(const uint8_t* bytes, size_t len, dsm_spm** out);
+void dsm_spm_free(dsm_spm*);
+const char* dsm_spm_last_error(const dsm_spm*);
+int dsm_spm_vocab_size(const dsm_spm*);
+int dsm_spm_special_ids(const dsm_spm*, int* unk, int* bos, int* eos, int* pad);
+int64_t dsm_spm_encode(const dsm_spm*, const char* utf8, size_t len, uint32_t* ids_out, size_t cap);
+int64_t dsm_spm_decode(const dsm_spm*, const uint32_t* ids, size_t n, char* out, size_t cap);
+
 /* text_tokenizer.decode_piece_ids (srv/batched_asr.rs:667): write the UTF-8 text of the pieces, return its length or <0.
- * Without one a Word carries the decimal piece ids separated by spaces. */
+ * The override of dsm_worker_set_tokenizer_file; with neither, a Word carries the decimal piece ids separated by spaces. */
 typedef int (*dsm_detok_fn)(void* user, const uint32_t* tokens, int n_tokens, char* out, size_t cap);
 
 typedef struct dsm_worker dsm_worker;
@@ -675,11 +718,18 @@ typedef struct dsm_worker_backend {
    * worker lets dsm_worker_step_encode run up to three frames ahead of dsm_worker_step_model; without them one. */
   int (*encode_async)(void* self, const float* pcm, const uint8_t* mask, int* ticket);
   int (*step_ticket)(void* self, int ticket, const uint8_t* mask, uint32_t* text_tokens_out, float* prs_out);
+  int text_out_vocab_size; /* the LM's text vocabulary, 0 = not known: dsm_worker_set_tokenizer_file checks against it */
 } dsm_worker_backend;
 int dsm_worker_create_with_backend(const dsm_worker_backend*, dsm_worker** out);
 void dsm_worker_destroy(dsm_worker*);
 const char* dsm_worker_last_error(const dsm_worker*);
 void dsm_worker_set_detokenizer(dsm_worker*, dsm_detok_fn, void* user);
+/* Word.text = the native decode of the word's tokens with this SentencePiece model (dsm_spm_decode).  A dsm_detok_fn, if set,
+ * still wins; with neither the decimal ids stay.  A token outside the model (the `?` of srv/batched_asr.rs:667, where the
+ * reference's loop ends) makes that step return DSM_ERR_STATE with the message.  DSM_ERR_IO / DSM_ERR_INVALID as
+ * dsm_spm_load; DSM_ERR_INVALID also when the model has more pieces than the backend's text_out_vocab_size (an engine-backed
+ * worker knows its own).  The previous tokenizer, if any, stays on failure. */
+int dsm_worker_set_tokenizer_file(dsm_worker*, const char* path);
 /* BatchedAsr::channels (:796-808) + the Init that handle_socket / handle_query send (:833,893).  Returns the slot
  * (batch_idx) or DSM_ERR_STATE when no slot is free ("Server at capacity - no free channels available", :875). */
 int dsm_worker_open(dsm_worker*, uint64_t* channel_id);
