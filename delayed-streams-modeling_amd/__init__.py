@@ -112,6 +112,12 @@ class Metrics(C.Structure):
                 ("capture_failures", C.c_uint64), ("capture_error", C.c_char * 96)]
 
 
+class SlotBlobInfo(C.Structure):
+    _fields_ = [("version", C.c_uint32), ("n_slots", C.c_uint32), ("flags", C.c_uint32), ("sig_words", C.c_uint32),
+                ("host_bytes", C.c_uint64), ("slot_bytes", C.c_uint64), ("total_bytes", C.c_uint64)]
+
+
+SLOT_BLOB_HAS_MODEL_MIMI = 1
 MSG_STEP, MSG_WORD, MSG_END_WORD = 0, 1, 2
 
 # Every symbol include/dsm.h declares (the "not gpu" tests check the library exports all of them).
@@ -121,6 +127,7 @@ ABI_SYMBOLS = [
     "dsm_asr_step_pcm", "dsm_asr_poll_msgs", "dsm_asr_reset_slot", "dsm_mimi_reset_slot", "dsm_sync",
     "dsm_get_metrics", "dsm_batch_size", "dsm_n_q", "dsm_mimi_encode_step_dev", "dsm_asr_step_tokens_dev",
     "dsm_streams_join", "dsm_debug_read", "dsm_debug_gemm_plan", "dsm_asr_step_pcm_dev", "dsm_prof_enable", "dsm_prof_read",
+    "dsm_asr_export_slots", "dsm_asr_import_slots", "dsm_asr_move_slots", "dsm_slot_blob_info",
     "dsm_asr_create_replica", "dsm_asr_set_seed", "dsm_debug_set_positions", "dsm_debug_set_text_tokens", "dsm_mimi_decode_step", "dsm_mimi_decode_step_dev",
     "dsm_lm_stream_groups", "dsm_debug_serialize_groups", "dsm_prof_read_device", "dsm_prof_timeline", "dsm_prof_timeline_read",
     "dsm_wav_decode", "dsm_mp3_decode", "dsm_mp3_decode_info", "dsm_mp3_probe", "dsm_resample", "dsm_pcm_decode",
@@ -222,6 +229,14 @@ def load_library(path=None):
     lib.dsm_asr_set_seed.argtypes = [vp, C.c_int, C.c_uint64]
     lib.dsm_asr_set_seed.restype = C.c_int
     lib.dsm_debug_set_text_tokens.argtypes = [vp, vp]
+    lib.dsm_asr_export_slots.argtypes = [vp, C.POINTER(C.c_int), C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.dsm_asr_import_slots.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_size_t]
+    lib.dsm_asr_move_slots.argtypes = [vp, C.POINTER(C.c_int), vp, C.POINTER(C.c_int), C.c_int]
+    lib.dsm_slot_blob_info.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(SlotBlobInfo)]
+    lib.dsm_mimi_encode_step_async.argtypes = [vp, fp, u8p, C.POINTER(C.c_int)]
+    lib.dsm_asr_step_tokens_ticket.argtypes = [vp, C.c_int, u8p, u32p, fp]
+    for name in ("dsm_asr_export_slots", "dsm_asr_import_slots", "dsm_asr_move_slots", "dsm_slot_blob_info"):
+        getattr(lib, name).restype = C.c_int
     lib.dsm_debug_set_text_tokens.restype = C.c_int
     lib.dsm_prof_enable.argtypes = [vp, C.c_uint]
     lib.dsm_prof_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
@@ -435,6 +450,18 @@ def config_tts_tiny(kv_bf16=1, cross_attention=False, cfg_rows=False, ca_dim=0, 
         cfg.cross_attention, cfg.ca_norm, cfg.ca_dim, cfg.ca_max_len = 1, ca_norm, ca_dim, 24
         cfg.cfg_rows = 1 if cfg_rows else 0
     return cfg
+
+
+def slot_blob_info(blob):
+    """dsm_slot_blob_info: header fields of a slot blob as a dict (host only, no device); DsmError for a malformed one."""
+    lib = load_library()
+    blob = bytes(blob)
+    info = SlotBlobInfo()
+    rc = lib.dsm_slot_blob_info(blob, len(blob), C.byref(info))
+    if rc < 0:
+        msg = lib.dsm_last_error(None)
+        raise DsmError(f"dsm error {rc}: {msg.decode() if msg else '?'}")
+    return {name: getattr(info, name) for name, _ in SlotBlobInfo._fields_}
 
 
 def _ptr(a):
@@ -947,6 +974,53 @@ class AsrEngine:
     def set_seed(self, slot, seed):
         """temperature > 0: restart the slot's Gumbel-noise stream (ChaCha12 keyed by seed_from_u64(seed))."""
         self._check(self.lib.dsm_asr_set_seed(self.h, slot, seed))
+
+    def encode_step_async(self, pcm, mask):
+        """dsm_mimi_encode_step_async: enqueue the frame's encode, return its ticket for step_tokens_ticket."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(self.B, FRAME_SIZE)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        ticket = C.c_int(-1)
+        self._check(self.lib.dsm_mimi_encode_step_async(self.h, _ptr(pcm), _ptr(mask), C.byref(ticket)))
+        return ticket.value
+
+    def step_tokens_ticket(self, ticket, mask):
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        text = np.zeros(self.B, dtype=np.uint32)
+        nh = self.cfg.extra_heads_num
+        prs = np.zeros((max(nh, 1), self.B), dtype=np.float32)
+        self._check(self.lib.dsm_asr_step_tokens_ticket(self.h, ticket, _ptr(mask), _ptr(text), _ptr(prs) if nh else None))
+        return text, prs[:nh]
+
+    # slot snapshots (include/dsm.h "slot snapshots"; INTEGRATION.md has the drain / compact / resume recipes)
+    @staticmethod
+    def _slot_list(slots):
+        slots = [int(s) for s in slots]
+        return (C.c_int * max(len(slots), 1))(*slots), len(slots)
+
+    def export_slots(self, slots):
+        """The listed slots' whole stream state as one blob (bytes).  The slots themselves are left as they are: reset them
+        (reset_batch_idx + mimi_reset_batch_idx) before another stream takes them."""
+        arr, n = self._slot_list(slots)
+        need = C.c_size_t(0)
+        self._check(self.lib.dsm_asr_export_slots(self.h, arr, n, None, 0, C.byref(need)))
+        buf = bytearray(need.value)  # a blob is ~100 MB per slot at the served presets: the library writes into it in place
+        self._check(self.lib.dsm_asr_export_slots(self.h, arr, n, (C.c_char * need.value).from_buffer(buf), need.value, C.byref(need)))
+        return bytes(buf)
+
+    def import_slots(self, slots, blob):
+        """Slot i of `blob` (export_slots of an engine of the same configuration; batch size and device may differ) into
+        slots[i].  DsmError, engine unchanged, when the blob does not fit."""
+        arr, n = self._slot_list(slots)
+        blob = bytes(blob)
+        self._check(self.lib.dsm_asr_import_slots(self.h, arr, n, blob, len(blob)))
+
+    def move_slots(self, src_slots, dst, dst_slots):
+        """This engine's src_slots[i] -> dst's dst_slots[i], device to device (same device only); dst may be self (a fork)."""
+        sa, n = self._slot_list(src_slots)
+        da, nd = self._slot_list(dst_slots)
+        if n != nd:
+            raise DsmError("move_slots: the two slot lists differ in length")
+        self._check(self.lib.dsm_asr_move_slots(self.h, sa, dst.h, da, n))
 
     def debug_set_text_tokens(self, tokens):
         """Teacher forcing: the text token every slot feeds back into its next step."""

@@ -140,6 +140,25 @@ struct DsmDevice {
     *out = reinterpret_cast<T*>(p);
     return 0;
   }
+  // hand back a dalloc / halloc before the context ends (a staging buffer that is being replaced by a larger one)
+  void dfree(void* p) {
+    if (!p) return;
+    {
+      std::lock_guard<std::mutex> lk(own_mu);
+      for (size_t i = 0; i < allocs.size(); ++i)
+        if (allocs[i] == p) { allocs.erase(allocs.begin() + (long)i); break; }
+    }
+    (void)hipFree(p);
+  }
+  void hfree(void* p) {
+    if (!p) return;
+    {
+      std::lock_guard<std::mutex> lk(own_mu);
+      for (size_t i = 0; i < pinned.size(); ++i)
+        if (pinned[i] == p) { pinned.erase(pinned.begin() + (long)i); break; }
+    }
+    (void)hipHostFree(p);
+  }
   int new_event(hipEvent_t* out, unsigned flags = hipEventDisableTiming) {
     HIPCHK_E(this, hipEventCreateWithFlags(out, flags));
     std::lock_guard<std::mutex> lk(own_mu);

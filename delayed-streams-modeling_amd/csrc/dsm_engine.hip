@@ -28,6 +28,7 @@
 #include "dsm_kernels.h"
 #include "dsm_numerics.h"
 #include "dsm_safetensors.h"
+#include "dsm_slot_blob.h"
 #include "dsm_spm.h"
 
 static thread_local std::string g_create_error;
@@ -183,6 +184,10 @@ struct MimiState {  // one per side (encoder-thread clone / model side)
   int ds_desc = -1;  // index of the downsample conv in descs
   bool first_call = true;
   uint8_t* mask = nullptr;  // device [B]
+  // [B], in being only once slots were imported while first_call still holds (dsm_asr_import_slots): 1 = the slot carries imported
+  // state, which the first call's replicate pad and zeroing must leave alone.  keep_h mirrors it on the host.
+  uint8_t* keep = nullptr;
+  std::vector<uint8_t> keep_h;
 };
 
 struct MimiDecState {  // Mimi::decode_step state, allocated on first use
@@ -294,6 +299,27 @@ struct dsm_engine : DsmDevice {
   int pipe_next = 0;
   bool pipe_ready = false;
   std::mutex pipe_mu;
+  // slot snapshots (dsm_asr_export_slots / import / move; dsm_slot_state.inc): the section table of a slot's state — LM, then
+  // mimi[0], then mimi[1] — on the host and on the device, and the staging buffers.  Built by the first call that needs it.
+  struct SlotXfer {
+    std::mutex mu;                    // one export / import / move per engine at a time
+    std::vector<SlotSection> secs;    // all three groups; mimi[1]'s bases stay null until that side exists
+    std::vector<uint32_t> sig;        // the blob signature of this configuration
+    int nsec_base = 0, nsec_side = 0; // LM + mimi[0]; one Mimi side
+    unsigned chunks_base = 0, chunks_side = 0;
+    size_t bytes_base = 0, bytes_side = 0;
+    // sections the importer range-checks
+    int sec_lm_idx = -1, sec_text_token = -1, sec_first_step = -1, sec_rng_pos = -1, sec_next_cb = -1, sec_mimi_idx = -1;
+    SlotSection* d_secs = nullptr;
+    bool d_has1 = false;              // the device table holds mimi[1]'s bases
+    char* d_stage = nullptr;
+    size_t d_stage_cap = 0;
+    char* h_stage = nullptr;          // pinned
+    size_t h_stage_cap = 0;
+    int* d_slots = nullptr;
+    int slots_cap = 0;
+    hipEvent_t ev_packed = nullptr;
+  } xfer;
 };
 
 // ----------------------------------------------------------------------------------------------
@@ -1097,6 +1123,7 @@ int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, 
 }  // namespace
 
 #include "dsm_engine_api.inc"
+#include "dsm_slot_state.inc"
 #include "dsm_tts.inc"
 #include "dsm_tts_request.inc"
 #include "dsm_speaker.inc"

@@ -289,7 +289,7 @@ int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
   // conv's concat buffer
   if (int rc = transformer_forward<float, float>(e, st, w.tr, s.tr, s.act, B, Tt, s.mask, s.cat_ds, cat_map(w.downsample))) return rc;
   if (s.first_call && w.downsample.S > 0) {  // replicate left pad on the module's first call
-    hipLaunchKernelGGL(conv_replicate_init_kernel, dim3(B), dim3(256), 0, st, s.h_descs[s.ds_desc]);
+    hipLaunchKernelGGL(conv_replicate_init_kernel, dim3(B), dim3(256), 0, st, s.h_descs[s.ds_desc], (const uint8_t*)s.keep);
     HIPCHK(hipGetLastError());
   }
   // ConvDownsample1d::step — core/conv.rs:552-554
@@ -318,8 +318,9 @@ int mimi_encode_body(dsm_engine* e, int side, hipStream_t st) {
   }
   // carried conv state: masked in-place shift of every concat buffer (core/conv.rs:347-367)
   if (!s.h_descs.empty()) {
+    // keep: null unless slots were imported before this side's first call (import_slots), and only looked at on that call
     hipLaunchKernelGGL(conv_state_shift_kernel, dim3(B, (unsigned)s.h_descs.size()), dim3(256), 0, st, s.descs, s.mask,
-                       s.first_call ? 1 : 0, nullptr);
+                       s.first_call ? 1 : 0, nullptr, (const uint8_t*)(s.first_call ? s.keep : nullptr));
     HIPCHK(hipGetLastError());
   }
   s.first_call = false;
@@ -442,7 +443,7 @@ int mimi_decode_body(DsmDevice* e, const MimiW& w, MimiDecState& s, int B, hipSt
     return rc;
   if (!s.h_descs.empty()) {
     hipLaunchKernelGGL(conv_state_shift_kernel, dim3(B, (unsigned)s.h_descs.size()), dim3(256), 0, st, s.descs, s.mask,
-                       s.first_call ? 1 : 0, s.started);
+                       s.first_call ? 1 : 0, s.started, (const uint8_t*)nullptr);
     HIPCHK(hipGetLastError());
   }
   s.first_call = false;
@@ -678,6 +679,10 @@ int reset_mimi_slot(dsm_engine* e, int side, hipStream_t st, int slot) {  // Mim
   if (!s.h_descs.empty()) {
     hipLaunchKernelGGL(conv_state_reset_kernel, dim3((unsigned)s.h_descs.size()), dim3(256), 0, st, s.descs, slot);
     HIPCHK(hipGetLastError());
+  }
+  if (s.keep && s.first_call && s.keep_h[slot]) {  // an imported slot reset before the side's first call is a fresh slot again
+    s.keep_h[slot] = 0;
+    HIPCHK(hipMemsetAsync(s.keep + slot, 0, 1, st));
   }
   // decode side of the same Mimi: the decoder transformer is NOT reset (the reference resets encoder_transformer twice
   // instead: core/mimi.rs:237-238)

@@ -2174,8 +2174,10 @@ struct ConvStateDesc {
 // started (optional, [B]): per-slot freshness instead of the module-level first call (the TTS decode path): the states of
 // a slot that has not started are zero already (allocation, slot reset), and this launch — the last one of a decode step, behind
 // every reader of the flag — records that an active slot has started.
+// keep (optional, [B], read on the module's first call only): a slot whose state was imported before that call
+// (dsm_asr_import_slots) — it is not a fresh slot, so an inactive one keeps its state instead of being zeroed.
 __global__ void conv_state_shift_kernel(const ConvStateDesc* __restrict__ descs, const uint8_t* __restrict__ active,
-                                        int first_call, uint8_t* __restrict__ started) {
+                                        int first_call, uint8_t* __restrict__ started, const uint8_t* __restrict__ keep) {
   const ConvStateDesc dsc = descs[blockIdx.y];
   const int b = blockIdx.x;
   float* base = dsc.cat + (long)b * dsc.bstride;
@@ -2185,15 +2187,17 @@ __global__ void conv_state_shift_kernel(const ConvStateDesc* __restrict__ descs,
     // S <= T for every conv of the model, so source and destination do not overlap
     for (int i = threadIdx.x; i < n; i += blockDim.x) base[i] = src[i];
     if (started && blockIdx.y == 0 && threadIdx.x == 0) started[b] = 1;
-  } else if (first_call && !started) {
+  } else if (first_call && !started && !(keep && keep[b])) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) base[i] = 0.0f;
   }
 }
 
 // first call of a replicate-padded conv (ConvDownsample1d, core/conv.rs:318-327,530): the left pad
 // repeats the first input frame of every slot
-__global__ void conv_replicate_init_kernel(ConvStateDesc dsc) {
+// keep (optional, [B]): slots whose left pad was imported (dsm_asr_import_slots) are left alone
+__global__ void conv_replicate_init_kernel(ConvStateDesc dsc, const uint8_t* __restrict__ keep) {
   const int b = blockIdx.x;
+  if (keep && keep[b]) return;
   float* base = dsc.cat + (long)b * dsc.bstride;
   const float* first = base + (long)dsc.S * dsc.C;
   for (int i = threadIdx.x; i < dsc.S * dsc.C; i += blockDim.x) base[i] = first[i % dsc.C];
@@ -2203,6 +2207,72 @@ __global__ void conv_state_reset_kernel(const ConvStateDesc* __restrict__ descs,
   const ConvStateDesc dsc = descs[blockIdx.x];
   float* base = dsc.cat + (long)slot * dsc.bstride;
   for (int i = threadIdx.x; i < dsc.S * dsc.C; i += blockDim.x) base[i] = 0.0f;
+}
+
+// ------------------------------------------------------------------------------------------
+// Slot snapshots (dsm_asr_export_slots / import / move): gather the state of n slots into one contiguous staging buffer,
+// or scatter it back, in ONE launch.  The engine describes a slot's state as a table of sections — per-slot byte ranges
+// `bytes` long, `stride` apart between slots, section i of slot s at base + s * stride — and gives each a 16-byte-aligned
+// offset `off` inside the slot's `slot_bytes` of staging.  Work is cut into kSlotChunk-byte pieces of one section; chunk0 is
+// the number of pieces in front of the section, so a workgroup finds the section of piece w by bisection.  Grid (pieces, n):
+// x is capped by the launcher and strides the rest.
+// The ring sections (megabytes, 16-byte aligned at both ends) move as uint4, four loads in flight per thread; a conv
+// state is a few floats at a 4-byte-aligned engine address (config_tiny: 6 floats) and moves as words; first_step is a byte.
+// A section's length is its own: nothing is stored past it, on either side — the staging gaps stay as the caller left them.
+// ------------------------------------------------------------------------------------------
+struct SlotSection {
+  char* base;
+  long stride, bytes, off;
+  unsigned chunk0, pad_;
+};
+constexpr long kSlotChunk = 16384;  // 256 threads x 4 x 16 bytes
+
+template <bool PACK>
+__device__ __forceinline__ void slot_state_copy(const SlotSection* __restrict__ secs, int nsec, unsigned total_chunks,
+                                                const int* __restrict__ slots, char* __restrict__ stage, long slot_bytes) {
+  const int j = blockIdx.y;
+  const long slot = slots[j];
+  for (unsigned w = blockIdx.x; w < total_chunks; w += gridDim.x) {
+    int lo = 0, hi = nsec - 1;  // the last section with chunk0 <= w
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (secs[mid].chunk0 <= w) lo = mid; else hi = mid - 1;
+    }
+    const SlotSection s = secs[lo];
+    const long at = (long)(w - s.chunk0) * kSlotChunk;
+    const long len = s.bytes - at < kSlotChunk ? s.bytes - at : kSlotChunk;
+    char* eng = s.base + slot * s.stride + at;
+    char* stg = stage + (long)j * slot_bytes + s.off + at;
+    const char* src = PACK ? eng : stg;
+    char* dst = PACK ? stg : eng;
+    const unsigned long al = (unsigned long)(uintptr_t)s.base | (unsigned long)s.stride | (unsigned long)s.bytes;
+    if ((al & 15) == 0) {  // `at`, `off`, slot_bytes and the staging base are multiples of 16 by construction
+      uint4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long o = ((long)u * 256 + threadIdx.x) * 16;
+        if (o < len) v[u] = *reinterpret_cast<const uint4*>(src + o);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long o = ((long)u * 256 + threadIdx.x) * 16;
+        if (o < len) *reinterpret_cast<uint4*>(dst + o) = v[u];
+      }
+    } else if ((al & 3) == 0) {
+      for (long o = (long)threadIdx.x * 4; o < len; o += (long)blockDim.x * 4)
+        *reinterpret_cast<uint32_t*>(dst + o) = *reinterpret_cast<const uint32_t*>(src + o);
+    } else {
+      for (long o = threadIdx.x; o < len; o += blockDim.x) dst[o] = src[o];
+    }
+  }
+}
+__global__ void __launch_bounds__(256) slot_state_pack_kernel(const SlotSection* __restrict__ secs, int nsec, unsigned total_chunks,
+                                                              const int* __restrict__ slots, char* __restrict__ stage, long slot_bytes) {
+  slot_state_copy<true>(secs, nsec, total_chunks, slots, stage, slot_bytes);
+}
+__global__ void __launch_bounds__(256) slot_state_unpack_kernel(const SlotSection* __restrict__ secs, int nsec, unsigned total_chunks,
+                                                                const int* __restrict__ slots, char* __restrict__ stage, long slot_bytes) {
+  slot_state_copy<false>(secs, nsec, total_chunks, slots, stage, slot_bytes);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -72,7 +72,7 @@ int spk_encode_body(dsm_tts* t, hipStream_t st, int c, int r) {
   }
   // ---- ConvDownsample1d::forward — core/conv.rs:527-547: the left pad of a clip repeats its first frame ----
   if (gd.S > 0) {
-    if (gd.replicate) hipLaunchKernelGGL(conv_replicate_init_kernel, dim3(c), dim3(256), 0, st, conv_desc(s.cat_ds, gd));
+    if (gd.replicate) hipLaunchKernelGGL(conv_replicate_init_kernel, dim3(c), dim3(256), 0, st, conv_desc(s.cat_ds, gd), (const uint8_t*)nullptr);
     HIPCHK(hipGetLastError());
   }
   if (int rc = run_conv(e, st, gd, s.cat_ds, c, s.latent, plain_map(c * r, d), nullptr, none, nullptr, none)) return rc;

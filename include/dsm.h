@@ -252,6 +252,45 @@ int dsm_mimi_reset_slot(dsm_engine*, int slot);
  * (slot b starts with seed 0x5EED0000 + b).  A reset of the slot does not touch the stream, like the reference's global generator. */
 int dsm_asr_set_seed(dsm_engine*, int slot, uint64_t seed);
 
+/* ---- slot snapshots: export, import and move a stream's state (this project's own; the reference is one process on one
+ * device and has no such call).  A snapshot holds everything a step of slot s reads that an earlier step of slot s wrote:
+ *   LM       the K / V ring rows of every layer, ring position and write index, first_step, the fed-back text token, the
+ *            one-step-shifted audio codes, the Gumbel stream's key and position;
+ *   Mimi     for the encoder-thread side always, for the model side once it exists (first dsm_asr_step_pcm[_dev]): the encoder
+ *            transformer's ring rows with position and index, and every carried conv state (the downsample conv's left pad too);
+ *   host     the word-assembly item (step index, pending word tokens, unended_word, last stop time).
+ * NOT in a snapshot: the Mimi DECODE state (dsm_mimi_decode_step), the activation scratch and anything else a step overwrites
+ * before it reads, the worker's channels (dsm_worker), captured graphs, metrics, and the TTS engine.
+ * After an import the stream continues bit for bit — codes, tokens, VAD, words — as if it had stayed where it was.  One
+ * exception, stated: a slot exported from a Mimi side that has never stepped and imported into a side that has behaves like a
+ * reset slot there (zero left pad) — the module-level first call that would have replicated its first frame cannot be moved.
+ * The blob (csrc/dsm_slot_blob.h) carries a signature of every configuration field that fixes a size or a
+ * meaning; batch size, dot_mode and the device may differ between exporter and importer.
+ *   dsm_asr_export_slots  waits for everything enqueued on the engine, packs the n slots with one kernel launch and copies the
+ *     blob to `buf`.  *needed (optional) receives the blob's size; buf NULL: size query only; cap < size: DSM_ERR_INVALID.
+ *     DSM_ERR_STATE while a dsm_mimi_encode_step_async ticket is outstanding.  The source slots are left untouched — the
+ *     caller resets them (dsm_asr_reset_slot + dsm_mimi_reset_slot) before reuse.
+ *   dsm_asr_import_slots  slot i of the blob goes to slots[i].  Everything is validated before anything is written:
+ *     DSM_ERR_INVALID — engine unchanged, dsm_last_error names the first mismatch — for a different signature, a truncated or
+ *     malformed blob, n different from the blob's, a slot out of range or listed twice, or an index-valued field out of range
+ *     (ring index >= context, text token / audio code outside its vocabulary, Gumbel position not a multiple of 16).  A blob
+ *     with the model-side Mimi brings that side into being here; one without resets that side of the slot.  Works on an
+ *     engine that has never stepped: the other slots then behave exactly as in a fresh engine.
+ *   dsm_asr_move_slots    src_slots[i] of src -> dst_slots[i] of dst on the SAME device (DSM_ERR_DEVICE otherwise: across
+ *     devices, export then import), through a device staging buffer, no host copy.  src == dst with disjoint lists forks a
+ *     stream.  Duplicate destination slots: DSM_ERR_INVALID.  Errors are reported on src (dsm_last_error(src)).
+ *   dsm_slot_blob_info    host only, no device needed: checks header and host section, fills *out. */
+#define DSM_SLOT_BLOB_HAS_MODEL_MIMI 1u
+#define DSM_SLOT_SIDE_PRISTINE0 1u
+struct dsm_slot_blob_info { /* no typedef: the function below has the name (struct tags are a namespace of their own in C) */
+  uint32_t version, n_slots, flags, sig_words;
+  uint64_t host_bytes, slot_bytes, total_bytes; /* host section, device payload per slot, the whole blob */
+};
+int dsm_asr_export_slots(dsm_engine*, const int* slots, int n, void* buf, size_t cap, size_t* needed);
+int dsm_asr_import_slots(dsm_engine*, const int* slots, int n, const void* buf, size_t len);
+int dsm_asr_move_slots(dsm_engine* src, const int* src_slots, dsm_engine* dst, const int* dst_slots, int n);
+int dsm_slot_blob_info(const void* buf, size_t len, struct dsm_slot_blob_info* out);
+
 /* Device::synchronize — srv/batched_asr.rs:238. */
 int dsm_sync(dsm_engine*);
 
