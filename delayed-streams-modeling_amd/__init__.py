@@ -142,6 +142,7 @@ ABI_SYMBOLS = [
     "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot", "dsm_tts_debug_read", "dsm_tts_get_metrics", "dsm_tts_set_sampling",
     "dsm_tts_set_ca_src", "dsm_tts_attach_mimi", "dsm_tts_step_pcm", "dsm_tts_recv_pcm", "dsm_tts_pcm_pending",
     "dsm_tts_attach_speaker_encoder", "dsm_tts_encode_voice", "dsm_tts_speaker_empty",
+    "dsm_tts_voice_create", "dsm_tts_voice_destroy", "dsm_tts_voice_info", "dsm_tts_set_voice",
     "dsm_tts_request_begin", "dsm_tts_request_push_words", "dsm_tts_request_close", "dsm_tts_run", "dsm_tts_collect",
     "dsm_tts_request_status",
     "dsm_tts_attach_conditioners", "dsm_tts_set_condition_lut", "dsm_tts_set_condition_cont", "dsm_tts_set_condition_padding",
@@ -322,6 +323,10 @@ def load_library(path=None):
     lib.dsm_tts_recv_pcm.argtypes = [vp, fp, u8p]
     lib.dsm_tts_pcm_pending.argtypes = [vp]
     lib.dsm_tts_attach_speaker_encoder.argtypes = [vp, C.c_int, C.c_char_p]
+    lib.dsm_tts_voice_create.argtypes = [vp, fp, C.c_int, C.POINTER(C.c_int)]
+    lib.dsm_tts_voice_destroy.argtypes = [vp, C.c_int]
+    lib.dsm_tts_voice_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    lib.dsm_tts_set_voice.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double]
     lib.dsm_tts_encode_voice.argtypes = [vp, fp, C.c_int, C.c_int, fp, C.c_int, C.POINTER(C.c_int)]
     lib.dsm_tts_speaker_empty.argtypes = [vp, fp, C.c_int, C.POINTER(C.c_int)]
     lib.dsm_tts_request_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -1255,6 +1260,36 @@ class TtsEngine:
         u = None if ca_src_uncond is None else np.ascontiguousarray(ca_src_uncond, dtype=np.float32)
         self._check(self.lib.dsm_tts_set_ca_src(self.h, slot, _ptr(a), 0 if a is None else a.shape[0], _ptr(u),
                                                 0 if u is None else u.shape[0], float(cfg_alpha)))
+
+    # ---- voices: a source projected once on the device, shared by the slots that attach to it ----
+    def voice_create(self, rows):
+        """ca_src rows [n][cond_dim] f32 -> a voice handle (> 0): the in_proj_kv projection of every layer, kept on the device."""
+        a = np.ascontiguousarray(rows, dtype=np.float32)
+        n = a.shape[0] if a.ndim == 2 else 0
+        v = C.c_int(0)
+        self._check(self.lib.dsm_tts_voice_create(self.h, _ptr(a) if n and a.size else None, n, C.byref(v)))
+        return v.value
+
+    def voice_destroy(self, voice):
+        self._check(self.lib.dsm_tts_voice_destroy(self.h, voice))
+
+    def voice_info(self, voice):
+        """(rows, batch rows attached, device bytes)"""
+        rows, refs, nbytes = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        self._check(self.lib.dsm_tts_voice_info(self.h, voice, C.byref(rows), C.byref(refs), C.byref(nbytes)))
+        return rows.value, refs.value, nbytes.value
+
+    def set_voice(self, slot, voice, uncond=0, cfg_alpha=0.0):
+        """set_ca_src by reference: the slot's rows read `voice` (and `uncond`, the second batch row of a guided request)."""
+        self._check(self.lib.dsm_tts_set_voice(self.h, slot, voice, uncond, float(cfg_alpha)))
+
+    def voice_from_clips(self, clips):
+        """encode_voice, then voice_create."""
+        return self.voice_create(self.encode_voice(clips))
+
+    def voice_empty(self):
+        """speaker_empty, then voice_create: the unconditional voice every guided request shares."""
+        return self.voice_create(self.speaker_empty())
 
     # ---- conditioners (core/conditioner.rs): one Condition::AddToInput per slot ----
     def attach_conditioners(self, descs, lm_path):

@@ -108,8 +108,11 @@ struct TransformerW {
 // serves them: `last` = source length - 1 plays start_pos (every one of the `len` rows is visible, no causal mask), `act`
 // = the row attends this step (it is active and has a source).  `att` [rows][d] holds the attention output; rows that never
 // attend keep the zeros they were created with, so their out_proj term is +0 (ca_src = None: the layer adds nothing, :753-760).
+// `src` (per layer, one entry per row, device memory) says where each row's block is: its private block in k / v, or a voice
+// shared with other rows (dsm_tts_voice.inc).  The attention launch reads the blocks through it, never through k / v directly.
 struct CaState {
   std::vector<void*> k, v;
+  std::vector<AttnRowSrc*> src;
   uint32_t* last = nullptr;
   uint8_t* act = nullptr;
   float* att = nullptr;
@@ -610,6 +613,7 @@ TransformerState group_view(const TransformerState& full, const dsm_transformer_
 CaState group_view(const CaState& full, int d_model, size_t kv_elem_bytes, int r0) {
   CaState v = full;
   offset_rings(v.k, v.v, (size_t)r0 * d_model * full.smax * kv_elem_bytes);  // [rows][H][smax][hd]
+  for (AttnRowSrc*& s : v.src) s += r0;
   v.last += r0; v.act += r0;
   v.att += (size_t)r0 * d_model;
   return v;
@@ -1125,6 +1129,7 @@ int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, 
 #include "dsm_engine_api.inc"
 #include "dsm_slot_state.inc"
 #include "dsm_tts.inc"
+#include "dsm_tts_voice.inc"
 #include "dsm_tts_request.inc"
 #include "dsm_speaker.inc"
 #include "dsm_tts_cond.inc"

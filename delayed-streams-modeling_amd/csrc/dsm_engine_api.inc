@@ -85,6 +85,8 @@ int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, 
   if (ca) {  // xs = residual + cross_attn.forward(norm_cross(xs), ca_src) — core/transformer.rs:753-760, :320-352
     AttnFused none{};
     none.nt = sizeof(KVT) == 2;  // as for the self-attention (transformer_forward)
+    none.src = ca->src[l];       // each row's block: private, or a voice it shares (read from device memory at every replay);
+                                 // the launch below passes no cache base, which is what sends the kernel to the table
     {
       GemmArgs a = base_args(L.ca_q, act.xn, plain_map(M, d), M);  // in_proj_q, (b, t, H, hd)
       a.Y = act.q; a.ymap = plain_map(M, d);
@@ -98,7 +100,7 @@ int transformer_layer_tail(DsmDevice* e, hipStream_t st, const TransformerW& w, 
     }
     // softmax(q k^T hd^-1/2) v over the row's source, no mask: the self-attention kernel on a "ring" that holds the
     // projected source, every row of it visible (canonical order as for the ring)
-    if (int rc = launch_attn<KVT>(e, st, ca->att, act.q, ca->k[l], ca->v[l], ca->last, ca->act, B, H, hd, T, ca->smax, d, none)) return rc;
+    if (int rc = launch_attn<KVT>(e, st, ca->att, act.q, nullptr, nullptr, ca->last, ca->act, B, H, hd, T, ca->smax, d, none)) return rc;
     GemmArgs a = base_args(L.ca_out, ca->att, plain_map(M, d), M);  // out_proj; gating = Normal
     a.res = act.x; a.rmap = plain_map(M, d);
     a.Y = act.x; a.ymap = plain_map(M, d);

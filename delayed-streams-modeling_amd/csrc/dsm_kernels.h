@@ -1113,6 +1113,19 @@ __global__ __launch_bounds__(256) void row_norm_kernel(float* __restrict__ y, co
 // One workgroup (4 waves) per (slot b, head h).  LPK = HD/8 lanes per key, G = 64/LPK keys per
 // wave-instruction, key j -> wave (j/G)%4, lane group j%G (canonical order, dsm_numerics.h).
 // ------------------------------------------------------------------------------------------
+// Where one batch row of a launch keeps its K / V when the rows do not sit in one [rows][H][ctx][hd] block: the [H][ctx][hd]
+// blocks of the row (TTS cross-attention: the row's private blocks, or a voice that several rows share — dsm_tts_voice.inc).
+// One 16-byte entry per row, read once per workgroup; it lives in device memory because a captured launch keeps its arguments.
+struct alignas(16) AttnRowSrc {
+  const void *k, *v;
+};
+// A table entry's pointer as what it is, a global address: built from plain bits the K / V accesses behind it would become flat_*
+// instructions (counted twice, checked against the LDS aperture) instead of global_* ones — for every launch of the kernel.
+template <typename KVT>
+__device__ __forceinline__ const KVT* attn_row_base(uint64_t bits) {
+  return (const KVT*)(const __attribute__((address_space(1))) KVT*)bits;
+}
+
 // T = 1 only: the QKV GEMM left its split-K slabs in place and this kernel finishes the job for its own (slot, head) —
 // ordered slab sums of the 3 x HD values, RoPE on q and k, K/V rows rounded into the ring cache at widx — before it
 // attends.  Same arithmetic, same order as gemm_reduce_kernel<KVT, EPI_QKV>; one launch and the q round trip less.
@@ -1124,6 +1137,10 @@ struct AttnFused {
   const uint32_t* widx;
   int nt;  // K / V rows with non-temporal loads (the bf16 rings)
   int q_only;  // the slabs hold a [M][d] query projection only (cross-attention, r04): no K / V rows, no RoPE, nothing scattered
+  // Row b's K / V sit at kcache / vcache + b * H * ctx * hd, or — for a launch that passes NO kcache (null) — where src[b] says.
+  // The kernels test kcache, not src: it shares a kernarg cache line with what they read first anyway, src sits in a line that
+  // the other launches (the STT hot path) then never wait for.
+  const AttnRowSrc* src;
 };
 
 // UNRB: keys per lane group and batch on a bf16 ring (8: 126 VGPRs, 4: 78).  The key -> (wave, lane group) assignment and the order
@@ -1139,6 +1156,17 @@ __global__ __launch_bounds__(256, 4) void attn_kernel(float* __restrict__ out, c
   constexpr int NW = 4, LPK = HD / 8, G = 64 / LPK;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int b = blockIdx.x / H, h = blockIdx.x % H;
+  // Row b's table entry, in flight across the `active` test: a VECTOR load on purpose (the uniform row index is handed over in a
+  // VGPR), so that it is counted with the load of active[b] and one wait covers both.  As a scalar load it was waited for on its
+  // own ahead of that load — one more memory round trip per launch (+14.5 us on the 16 launches of a B = 32 step: DESIGN.md
+  // section 5.4.1, "The kernels", has the numbers and the tool that repeats them).  Both forms compute the same values: once a
+  // compiler overlaps the scalar load's wait with the `active` load, plain `fq.src[b]` may come back.
+  uint4 rs_kv = {0u, 0u, 0u, 0u};
+  if (!kcache) {
+    int bv = b;
+    asm volatile("" : "+v"(bv));
+    rs_kv = *reinterpret_cast<const uint4*>(fq.src + bv);
+  }
   // optional device-clock bracket of the whole launch (dsm_prof_read_device): first workgroup in, last one out.
   // HIP events around a launch also count the time it queues behind other streams' kernels; this does not.
   // Only the first 256 workgroups race for the start stamp and the last 1024 for the end stamp (dispatch is in index
@@ -1163,6 +1191,12 @@ __global__ __launch_bounds__(256, 4) void attn_kernel(float* __restrict__ out, c
 
   const KVT* Kb = kcache + ((long)b * H + h) * ctx * HD;
   const KVT* Vb = vcache + ((long)b * H + h) * ctx * HD;
+  if (!kcache) {  // the row's own K / V block (every lane loaded the same entry: back to scalar registers)
+    const uint64_t kp = ((uint64_t)__builtin_amdgcn_readfirstlane(rs_kv.y) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane(rs_kv.x);
+    const uint64_t vp = ((uint64_t)__builtin_amdgcn_readfirstlane(rs_kv.w) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane(rs_kv.z);
+    Kb = attn_row_base<KVT>(kp) + (long)h * ctx * HD;
+    Vb = attn_row_base<KVT>(vp) + (long)h * ctx * HD;
+  }
   if (T == 1 && fq.ws) {
     // row m = b of the [M][3d] QKV product: q at n = h*HD + i, k at d + ..., v at 2d + ... (core/batched_transformer.rs:77-82)
     if (tid < (fq.q_only ? HD / 4 : 3 * HD / 4)) {
@@ -1362,6 +1396,10 @@ __global__ __launch_bounds__(256) void attn_small_kernel(float* __restrict__ out
   const float scale = (float)(1.0 / sqrt((double)HD));
   const KVT* Kb = kcache + ((long)b * H + h) * ctx * HD;
   const KVT* Vb = vcache + ((long)b * H + h) * ctx * HD;
+  if (!kcache) {  // the row's own K / V block, as in attn_kernel
+    Kb = attn_row_base<KVT>((uint64_t)fq.src[b].k) + (long)h * ctx * HD;
+    Vb = attn_row_base<KVT>((uint64_t)fq.src[b].v) + (long)h * ctx * HD;
+  }
   if (fq.ws) {  // attn_kernel's prologue, lane for thread
     if (on && lane < (fq.q_only ? HD / 4 : 3 * HD / 4)) {
       const int part = lane / (HD / 4), i0 = 4 * (lane % (HD / 4));

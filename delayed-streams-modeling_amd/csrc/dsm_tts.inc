@@ -72,7 +72,21 @@ struct dsm_tts : DsmDevice {
   // cross attention + guidance (r03): per-row projected sources, per-slot guidance
   CaState ca;                         // full-batch view (groups take row-offset copies)
   float *ca_src_dev = nullptr, *ca_kv_tmp = nullptr;  // staging of dsm_tts_set_ca_src: [smax][ca_dim], [smax][2d]
-  std::vector<int> ca_len;            // [R] host mirror: rows of the batch row's source (0 = None)
+  std::vector<int> ca_len;            // [R] host mirror: rows of the batch row's source (0 = None), private or a voice's
+  // Voices (dsm_tts_voice.inc): a source projected once into device memory of its own, [layer][K, V][H][smax][hd] in the cache
+  // dtype, that any number of batch rows read by reference.  ca_src_tab [layer][R] (ca.src[l] points into it) is what every
+  // cross-attention launch — captured or not — reads a row's K / V base from: the row's private block from create on, a
+  // voice's while the row is attached.
+  struct Voice {
+    int handle = 0, rows = 0, refs = 0;  // refs: batch rows whose table entries point here
+    uint8_t* mem = nullptr;
+    size_t bytes = 0;
+  };
+  std::vector<Voice> voices;
+  int next_voice = 1;                 // handles count up and are never reused
+  std::vector<int> row_voice;         // [R] the voice a batch row reads (0: its private block)
+  AttnRowSrc* ca_src_tab = nullptr;
+  std::vector<AttnRowSrc> src_stage;  // [rps][layers] host side of a slot's table uploads (kept here: the copies are asynchronous)
   std::vector<uint8_t> cfg_on;        // [B]
   uint8_t* d_cfg_on = nullptr;
   float *d_cfg_fa = nullptr, *d_cfg_fb = nullptr, *mixed = nullptr, *dmixed = nullptr;  // [B], [B], [B][Vt], [B][V]
@@ -372,6 +386,23 @@ int tts_create_impl(dsm_tts* t, const dsm_tts_config* cfg, int device_id, int ba
       if ((rc = e->dalloc(&v, (size_t)R * d * smax * kv_elem))) return rc;
       t->ca.k[l] = k;
       t->ca.v[l] = v;
+    }
+    {  // every row starts on its private block (the identity table)
+      const int L = c.lm.num_layers;
+      const size_t blk = (size_t)d * smax * kv_elem;
+      std::vector<AttnRowSrc> tab((size_t)L * R);
+      for (int l = 0; l < L; ++l)
+        for (int r = 0; r < R; ++r) {
+          AttnRowSrc& s = tab[(size_t)l * R + r];
+          s = AttnRowSrc{};
+          s.k = (const uint8_t*)t->ca.k[l] + (size_t)r * blk;
+          s.v = (const uint8_t*)t->ca.v[l] + (size_t)r * blk;
+        }
+      if ((rc = e->upload(&t->ca_src_tab, tab.data(), tab.size()))) return rc;
+      t->ca.src.resize(L);
+      for (int l = 0; l < L; ++l) t->ca.src[l] = t->ca_src_tab + (size_t)l * R;
+      t->row_voice.assign(R, 0);
+      t->src_stage.assign((size_t)rps * L, AttnRowSrc{});
     }
     if ((rc = e->dalloc(&t->ca.last, R))) return rc;
     if ((rc = e->dalloc(&t->ca.att, (size_t)R * d))) return rc;
@@ -925,9 +956,16 @@ int dsm_tts_set_sampling(dsm_tts* t, int slot, int top_k, float temperature, uin
 }  // extern "C" (reopened below)
 
 namespace {
-// compute_kv(CaSrc::Tokens(src)) of one batch row into its block of every layer's source cache (core/transformer.rs:299-318)
+// A voice's K (kv = 0) or V (kv = 1) block of layer l, [H][smax][hd] in the cache dtype
+uint8_t* tts_voice_block(const dsm_tts* t, const dsm_tts::Voice& v, int l, int kv) {
+  const size_t blk = (size_t)t->cfg.lm.d_model * t->ca.smax * (t->cfg.kv_bf16 ? 2 : 4);
+  return v.mem + ((size_t)2 * l + kv) * blk;
+}
+
+// compute_kv(CaSrc::Tokens(src)) (core/transformer.rs:299-318) into every layer's [H][smax][hd] block of a voice, or (voice ==
+// nullptr) of batch row `row`'s private part of the source cache: one code path, so that a voice holds a private row's bits
 template <typename KVT>
-int tts_project_ca_row(dsm_tts* t, hipStream_t st, int row, const float* src, int n) {
+int tts_project_ca_row(dsm_tts* t, hipStream_t st, int row, const dsm_tts::Voice* voice, const float* src, int n) {
   DsmDevice* e = t;
   const dsm_tts_config& c = t->cfg;
   const int d = c.lm.d_model, H = c.lm.num_heads, hd = d / H, kvd = c.ca_dim > 0 ? c.ca_dim : d, smax = t->ca.smax;
@@ -936,12 +974,53 @@ int tts_project_ca_row(dsm_tts* t, hipStream_t st, int row, const float* src, in
     GemmArgs a = base_args(t->lm.tr.layers[l].ca_kv, t->ca_src_dev, plain_map(n, kvd), n);
     a.Y = t->ca_kv_tmp; a.ymap = plain_map(n, 2 * d);
     if (int rc = gemm_store<uint16_t>(e, st, a, kvd % 32 == 0)) return rc;
-    KVT* kc = reinterpret_cast<KVT*>(t->ca.k[l]) + (size_t)row * H * smax * hd;
-    KVT* vc = reinterpret_cast<KVT*>(t->ca.v[l]) + (size_t)row * H * smax * hd;
+    KVT* kc = voice ? reinterpret_cast<KVT*>(tts_voice_block(t, *voice, l, 0)) : reinterpret_cast<KVT*>(t->ca.k[l]) + (size_t)row * H * smax * hd;
+    KVT* vc = voice ? reinterpret_cast<KVT*>(tts_voice_block(t, *voice, l, 1)) : reinterpret_cast<KVT*>(t->ca.v[l]) + (size_t)row * H * smax * hd;
     const long tot = (long)n * d;
     hipLaunchKernelGGL(ca_kv_scatter_kernel<KVT>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, t->ca_kv_tmp, kc, vc, n, d, hd, smax);
     HIPCHK(hipGetLastError());
   }
+  return 0;
+}
+
+dsm_tts::Voice* tts_find_voice(dsm_tts* t, int handle) {
+  for (dsm_tts::Voice& v : t->voices)
+    if (v.handle == handle) return &v;
+  return nullptr;
+}
+
+// Batch row `row` reads `voice` from now on, or (nullptr) its private block again: its entry of every layer's table in one
+// strided upload, and the reference counts.  Nothing else is copied.  Only enqueues (the entries wait in src_stage, one part per
+// row of a slot): the caller synchronises the stream before it touches another slot.
+int tts_point_row(dsm_tts* t, hipStream_t st, int row, dsm_tts::Voice* voice) {
+  DsmDevice* e = t;
+  const int have = t->row_voice[row], want = voice ? voice->handle : 0;
+  if (have == want) return 0;
+  const int L = t->cfg.lm.num_layers, R = t->R;
+  const size_t blk = (size_t)t->cfg.lm.d_model * t->ca.smax * (t->cfg.kv_bf16 ? 2 : 4);
+  AttnRowSrc* ent = t->src_stage.data() + (size_t)(row % t->rps) * L;
+  for (int l = 0; l < L; ++l) {
+    ent[l].k = voice ? tts_voice_block(t, *voice, l, 0) : (uint8_t*)t->ca.k[l] + (size_t)row * blk;
+    ent[l].v = voice ? tts_voice_block(t, *voice, l, 1) : (uint8_t*)t->ca.v[l] + (size_t)row * blk;
+  }
+  HIPCHK(hipMemcpy2DAsync(t->ca_src_tab + row, sizeof(AttnRowSrc) * (size_t)R, ent, sizeof(AttnRowSrc), sizeof(AttnRowSrc), (size_t)L,
+                          hipMemcpyHostToDevice, st));
+  if (dsm_tts::Voice* old = tts_find_voice(t, have)) --old->refs;
+  if (voice) ++voice->refs;
+  t->row_voice[row] = want;
+  return 0;
+}
+
+// The slot's guidance: Tensor * f64 = affine(mul as f32, 0.), the two factors of l0 * a - l1 * (a - 1.) in f32
+int tts_upload_guidance(dsm_tts* t, hipStream_t st, int slot, bool guided, double cfg_alpha) {
+  DsmDevice* e = t;
+  const uint8_t on = guided ? 1 : 0;
+  const float fa = (float)cfg_alpha, fb = (float)(cfg_alpha - 1.);
+  HIPCHK(hipMemcpyAsync(t->d_cfg_on + slot, &on, 1, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t->d_cfg_fa + slot, &fa, sizeof fa, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t->d_cfg_fb + slot, &fb, sizeof fb, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  t->cfg_on[slot] = on;
   return 0;
 }
 }  // namespace
@@ -977,8 +1056,9 @@ int dsm_tts_set_ca_src(dsm_tts* t, int slot, const float* ca_src, int n, const f
   for (int j = 0; j < t->rps; ++j) {
     const int row = slot * t->rps + j, len = j == 0 ? n : n_uncond;
     const float* src = j == 0 ? ca_src : ca_src_uncond;
+    if (int rc = tts_point_row(t, st, row, nullptr)) return rc;  // a row on a voice (dsm_tts_set_voice) lets go of it first
     if (len > 0) {
-      const int rc = with_kv_type(c.kv_bf16 != 0, [&](auto kv) { return tts_project_ca_row<decltype(kv)>(t, st, row, src, len); });
+      const int rc = with_kv_type(c.kv_bf16 != 0, [&](auto kv) { return tts_project_ca_row<decltype(kv)>(t, st, row, nullptr, src, len); });
       if (rc) return rc;
       HIPCHK(hipStreamSynchronize(st));  // the staging buffers are reused by the next row; `src` is the caller's memory
     } else if (t->ca_len[row] > 0) {
@@ -990,15 +1070,7 @@ int dsm_tts_set_ca_src(dsm_tts* t, int slot, const float* ca_src, int n, const f
     HIPCHK(hipStreamSynchronize(st));
     t->ca_len[row] = len;
   }
-  // Tensor * f64 = affine(mul as f32, 0.): the two factors of l0 * a - l1 * (a - 1.) in f32
-  const uint8_t on = n_uncond > 0 ? 1 : 0;
-  const float fa = (float)cfg_alpha, fb = (float)(cfg_alpha - 1.);
-  HIPCHK(hipMemcpyAsync(t->d_cfg_on + slot, &on, 1, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(t->d_cfg_fa + slot, &fa, sizeof fa, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(t->d_cfg_fb + slot, &fb, sizeof fb, hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  t->cfg_on[slot] = on;
-  return 0;
+  return tts_upload_guidance(t, st, slot, n_uncond > 0, cfg_alpha);
 }
 
 int dsm_tts_reset_slot(dsm_tts* t, int slot) {

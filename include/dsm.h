@@ -399,6 +399,34 @@ int dsm_tts_set_sampling(dsm_tts*, int slot, int top_k, float temperature, uint6
  *     core/lm.rs:718-721: Tensor * f64 = affine(mul as f32, 0)), sampling once per slot.
  * Needs cfg.cross_attention; n, n_uncond <= ca_max_len.  dsm_tts_reset_slot clears both (a fresh State). */
 int dsm_tts_set_ca_src(dsm_tts*, int slot, const float* ca_src, int n, const float* ca_src_uncond, int n_uncond, double cfg_alpha);
+/* Voices: a source projected ONCE into device memory of its own, which any number of slots attach to by reference.
+ * dsm_tts_set_ca_src pays the in_proj_kv projection of every layer for every request and gives every batch row a private copy;
+ * a deployment has a handful of voices and one unconditional source for all guided requests.  The reference has no such
+ * object: its voice cache (srv/tts.rs:41-60, 702-744, ca_srcs / dynamic_ca_srcs) holds un-projected rows and compute_kv runs
+ * on them every step.  A voice holds, bit for bit, what dsm_tts_set_ca_src would have written for the same rows (same GEMM, same
+ * scatter kernel, another destination), so a slot computes the same tokens either way.
+ *   dsm_tts_voice_create   compute_kv(CaSrc::Tokens(ca_src)) (core/transformer.rs:299-318) for every main-LM layer into
+ *     [H][ca_max_len][hd] blocks for K and for V in the cache dtype (kv_bf16).  *voice_out: the handle, > 0 and never reused
+ *     during the engine's life (0 = none).  Synchronous, on the model stream between steps, like dsm_tts_set_ca_src /
+ *     dsm_tts_encode_voice; a generation in progress is not disturbed.  DSM_ERR_STATE without cfg.cross_attention;
+ *     DSM_ERR_INVALID for n < 1, n > ca_max_len or NULL rows; an allocation failure creates nothing and leaves the engine as it was.
+ *   dsm_tts_set_voice      the slot's rows read `voice` (batch row 0) and `voice_uncond` (batch row 1; 0 = no guidance) from now
+ *     on.  Preconditions and errors of dsm_tts_set_ca_src: a fresh slot (step index 0) unless both are 0, which clears like
+ *     NULL rows do; voice_uncond needs cfg_rows = 1 and a conditional voice; cfg_alpha is stored as the same two f32 factors.
+ *     DSM_ERR_INVALID for an unknown or destroyed handle.  No GEMM and no copy of K / V: the row's base pointers (one small
+ *     table entry per layer), its length and the guidance flag and factors are uploaded.  Replaces whatever the slot had
+ *     (private rows or other voices) and counts one reference per batch row that points at a voice.  dsm_tts_set_ca_src (rows
+ *     or NULL), dsm_tts_reset_slot and a later dsm_tts_set_voice drop the slot's references.
+ *   dsm_tts_voice_destroy  DSM_ERR_STATE ("in use by n rows") while referenced, nothing freed; else waits for the model stream
+ *     and frees.  dsm_tts_destroy frees what is left.
+ *   dsm_tts_voice_info     rows, current references, device bytes (any of the three may be NULL); DSM_ERR_INVALID for a bad
+ *     handle.  The bytes are those of the K / V blocks, 2 * layers * d_model * ca_max_len * element size — what one batch row's
+ *     private blocks take — without the 256 bytes of slack every device allocation of the engine carries.
+ * Rows attached to one voice read the same addresses, so its K / V are shared in the caches. */
+int dsm_tts_voice_create(dsm_tts*, const float* ca_src /* host [n][cond_dim] f32 */, int n, int* voice_out);
+int dsm_tts_voice_destroy(dsm_tts*, int voice);
+int dsm_tts_voice_info(dsm_tts*, int voice, int* rows, int* refs, size_t* device_bytes);
+int dsm_tts_set_voice(dsm_tts*, int slot, int voice, int voice_uncond /* 0 = no guidance */, double cfg_alpha);
 /* Generated frames to PCM — what the reference's TTS worker does with every step's tokens: a second thread receives
  * state.last_audio_tokens() and runs Mimi::decode_step on them (srv/tts.rs:528-544, core/mimi.rs:217-225) while the inference
  * loop is already in its next step.
@@ -430,9 +458,11 @@ int dsm_tts_recv_pcm(dsm_tts*, float* pcm_out, uint8_t* pcm_valid_out);
 int dsm_tts_pcm_pending(dsm_tts*);
 /* Voice clips to cross-attention rows — what the reference's server does on every voice-cache miss (srv/tts.rs:702-778,
  * 946-964) before a request's first step.  The rows go to dsm_tts_set_ca_src: ca_src from dsm_tts_encode_voice, ca_src_uncond
- * from dsm_tts_speaker_empty (srv/tts.rs:833-838).  Caching them per voice stays with the caller (the reference's
- * dynamic_ca_srcs cache lives in the server).  cond_dim = ca_dim if non-zero, else lm.d_model.  Rows are f32, the dtype
- * dsm_tts_set_ca_src takes: the reference's final to_dtype(self.dtype) (bf16 on its GPU path) is NOT applied.
+ * from dsm_tts_speaker_empty (srv/tts.rs:833-838) — or, to pay the projection once per voice instead of once per request,
+ * to dsm_tts_voice_create: the engine then keeps the projected voice on the device and requests attach to it with
+ * dsm_tts_set_voice (which voice belongs to which name stays with the caller, like the reference's dynamic_ca_srcs map).
+ * cond_dim = ca_dim if non-zero, else lm.d_model.  Rows are f32, the dtype dsm_tts_set_ca_src takes: the reference's final
+ * to_dtype(self.dtype) (bf16 on its GPU path) is NOT applied.
  *   dsm_tts_attach_speaker_encoder   SpeakerEncoder::new — core/tts_streaming.rs:346-372, srv/tts.rs:311-333.  The speaker
  *     tokenizer is the Mimi attached with dsm_tts_attach_mimi, as in the shipped configuration (configs/tts/config-tts.toml:17-18
  *     names one file twice).  Reads condition_provider.conditioners.speaker_wavs.{output_proj.weight [cond_dim][dimension],
