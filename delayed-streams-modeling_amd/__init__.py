@@ -117,7 +117,14 @@ class SlotBlobInfo(C.Structure):
                 ("host_bytes", C.c_uint64), ("slot_bytes", C.c_uint64), ("total_bytes", C.c_uint64)]
 
 
+class TtsSlotBlobInfo(C.Structure):
+    _fields_ = [("version", C.c_uint32), ("n_slots", C.c_uint32), ("flags", C.c_uint32), ("sig_words", C.c_uint32),
+                ("slices", C.c_uint32), ("reserved", C.c_uint32),
+                ("host_bytes", C.c_uint64), ("slot_bytes", C.c_uint64), ("total_bytes", C.c_uint64)]
+
+
 SLOT_BLOB_HAS_MODEL_MIMI = 1
+TTS_SLOT_BLOB_HAS_MIMI_DEC = 1
 MSG_STEP, MSG_WORD, MSG_END_WORD = 0, 1, 2
 
 # Every symbol include/dsm.h declares (the "not gpu" tests check the library exports all of them).
@@ -150,6 +157,7 @@ ABI_SYMBOLS = [
     "dsm_spm_load", "dsm_spm_load_bytes", "dsm_spm_free", "dsm_spm_last_error", "dsm_spm_vocab_size", "dsm_spm_special_ids",
     "dsm_spm_encode", "dsm_spm_decode", "dsm_worker_set_tokenizer_file",
     "dsm_tts_attach_tokenizer", "dsm_tts_request_push_text", "dsm_tts_word_text",
+    "dsm_tts_slot_blob_info",
 ]
 TTS_COND_LUT, TTS_COND_CONTINUOUS = 0, 1  # DSM_TTS_COND_*
 TTS_RUN_MAX = 16  # DSM_TTS_RUN_MAX
@@ -357,6 +365,8 @@ def load_library(path=None):
     lib.dsm_tts_request_push_text.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]
     lib.dsm_tts_word_text.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     lib.dsm_tts_word_text.restype = C.c_int64
+    lib.dsm_tts_slot_blob_info.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(TtsSlotBlobInfo)]
+    lib.dsm_tts_slot_blob_info.restype = C.c_int
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
         getattr(lib, name).restype = C.c_int
@@ -467,6 +477,18 @@ def slot_blob_info(blob):
         msg = lib.dsm_last_error(None)
         raise DsmError(f"dsm error {rc}: {msg.decode() if msg else '?'}")
     return {name: getattr(info, name) for name, _ in SlotBlobInfo._fields_}
+
+
+def tts_slot_blob_info(blob):
+    """dsm_tts_slot_blob_info: header fields of a TTS slot blob as a dict (host only, no device); DsmError for a malformed one."""
+    lib = load_library()
+    blob = bytes(blob)
+    info = TtsSlotBlobInfo()
+    rc = lib.dsm_tts_slot_blob_info(blob, len(blob), C.byref(info))
+    if rc < 0:
+        msg = lib.dsm_tts_last_error(None)
+        raise DsmError(f"dsm error {rc}: {msg.decode() if msg else '?'}")
+    return {name: getattr(info, name) for name, _ in TtsSlotBlobInfo._fields_ if name != "reserved"}
 
 
 def _ptr(a):

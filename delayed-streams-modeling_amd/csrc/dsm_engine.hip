@@ -29,6 +29,7 @@
 #include "dsm_numerics.h"
 #include "dsm_safetensors.h"
 #include "dsm_slot_blob.h"
+#include "dsm_tts_slot_blob.h"
 #include "dsm_spm.h"
 
 static thread_local std::string g_create_error;
@@ -1130,6 +1131,7 @@ int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, 
 #include "dsm_slot_state.inc"
 #include "dsm_tts.inc"
 #include "dsm_tts_voice.inc"
+#include "dsm_tts_slot_state.inc"
 #include "dsm_tts_request.inc"
 #include "dsm_speaker.inc"
 #include "dsm_tts_cond.inc"

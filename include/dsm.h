@@ -260,7 +260,7 @@ int dsm_asr_set_seed(dsm_engine*, int slot, uint64_t seed);
  *            transformer's ring rows with position and index, and every carried conv state (the downsample conv's left pad too);
  *   host     the word-assembly item (step index, pending word tokens, unended_word, last stop time).
  * NOT in a snapshot: the Mimi DECODE state (dsm_mimi_decode_step), the activation scratch and anything else a step overwrites
- * before it reads, the worker's channels (dsm_worker), captured graphs, metrics, and the TTS engine.
+ * before it reads, the worker's channels (dsm_worker), captured graphs, metrics, and the TTS engine (whose blob format, not yet its calls, is dsm_tts_slot_blob_info below).
  * After an import the stream continues bit for bit — codes, tokens, VAD, words — as if it had stayed where it was.  One
  * exception, stated: a slot exported from a Mimi side that has never stepped and imported into a side that has behaves like a
  * reset slot there (zero left pad) — the module-level first call that would have replicated its first frame cannot be moved.
@@ -427,6 +427,20 @@ int dsm_tts_voice_create(dsm_tts*, const float* ca_src /* host [n][cond_dim] f32
 int dsm_tts_voice_destroy(dsm_tts*, int voice);
 int dsm_tts_voice_info(dsm_tts*, int voice, int* rows, int* refs, size_t* device_bytes);
 int dsm_tts_set_voice(dsm_tts*, int slot, int voice, int voice_uncond /* 0 = no guidance */, double cfg_alpha);
+/* ---- The TTS slot blob: the container a generation's slot state travels in (csrc/dsm_tts_slot_blob.h; DESIGN.md section 7.2
+ * has the table of state it is laid out for and the layout).  Same conventions as the STT blob above — little-endian, 16-byte
+ * aligned sections, a signature of every configuration field that fixes a size or a meaning, an importer that never reads an
+ * offset from the blob — with a magic of its own: dsm_slot_blob_info and dsm_asr_import_slots refuse a TTS blob with "bad
+ * magic", and dsm_tts_slot_blob_info refuses an STT blob the same way.  The engine calls that fill and consume such a blob
+ * (export, import, move) are NOT in the library yet: only the format, its writer and its checked reader are.
+ *   dsm_tts_slot_blob_info  host only, no device needed: checks header and host section (every count against its bound, the
+ *     sizes against each other and against `len`), fills *out.  DSM_ERR_INVALID with dsm_tts_last_error(NULL) naming the fault. */
+#define DSM_TTS_SLOT_BLOB_HAS_MIMI_DEC 1u
+struct dsm_tts_slot_blob_info {
+  uint32_t version, n_slots, flags, sig_words, slices /* dep_num_slices */, reserved;
+  uint64_t host_bytes, slot_bytes, total_bytes; /* host section, device payload per slot, the whole blob */
+};
+int dsm_tts_slot_blob_info(const void* buf, size_t len, struct dsm_tts_slot_blob_info* out);
 /* Generated frames to PCM — what the reference's TTS worker does with every step's tokens: a second thread receives
  * state.last_audio_tokens() and runs Mimi::decode_step on them (srv/tts.rs:528-544, core/mimi.rs:217-225) while the inference
  * loop is already in its next step.
