@@ -467,28 +467,25 @@ def config_tts_tiny(kv_bf16=1, cross_attention=False, cfg_rows=False, ca_dim=0, 
     return cfg
 
 
-def slot_blob_info(blob):
-    """dsm_slot_blob_info: header fields of a slot blob as a dict (host only, no device); DsmError for a malformed one."""
+def _blob_info(blob, info, call, last_error):
+    """One of the two *_slot_blob_info calls on `blob`: the filled info struct as a dict, DsmError for a malformed blob."""
     lib = load_library()
     blob = bytes(blob)
-    info = SlotBlobInfo()
-    rc = lib.dsm_slot_blob_info(blob, len(blob), C.byref(info))
+    rc = getattr(lib, call)(blob, len(blob), C.byref(info))
     if rc < 0:
-        msg = lib.dsm_last_error(None)
+        msg = getattr(lib, last_error)(None)
         raise DsmError(f"dsm error {rc}: {msg.decode() if msg else '?'}")
-    return {name: getattr(info, name) for name, _ in SlotBlobInfo._fields_}
+    return {name: getattr(info, name) for name, _ in info._fields_ if name != "reserved"}
+
+
+def slot_blob_info(blob):
+    """dsm_slot_blob_info: header fields of a slot blob as a dict (host only, no device); DsmError for a malformed one."""
+    return _blob_info(blob, SlotBlobInfo(), "dsm_slot_blob_info", "dsm_last_error")
 
 
 def tts_slot_blob_info(blob):
     """dsm_tts_slot_blob_info: header fields of a TTS slot blob as a dict (host only, no device); DsmError for a malformed one."""
-    lib = load_library()
-    blob = bytes(blob)
-    info = TtsSlotBlobInfo()
-    rc = lib.dsm_tts_slot_blob_info(blob, len(blob), C.byref(info))
-    if rc < 0:
-        msg = lib.dsm_tts_last_error(None)
-        raise DsmError(f"dsm error {rc}: {msg.decode() if msg else '?'}")
-    return {name: getattr(info, name) for name, _ in TtsSlotBlobInfo._fields_ if name != "reserved"}
+    return _blob_info(blob, TtsSlotBlobInfo(), "dsm_tts_slot_blob_info", "dsm_tts_last_error")
 
 
 def _ptr(a):

@@ -31,6 +31,7 @@
 #include "dsm_slot_blob.h"
 #include "dsm_tts_slot_blob.h"
 #include "dsm_spm.h"
+#include "dsm_slot_xfer.inc"
 
 static thread_local std::string g_create_error;
 
@@ -304,26 +305,11 @@ struct dsm_engine : DsmDevice {
   bool pipe_ready = false;
   std::mutex pipe_mu;
   // slot snapshots (dsm_asr_export_slots / import / move; dsm_slot_state.inc): the section table of a slot's state — LM, then
-  // mimi[0], then mimi[1] — on the host and on the device, and the staging buffers.  Built by the first call that needs it.
-  struct SlotXfer {
-    std::mutex mu;                    // one export / import / move per engine at a time
-    std::vector<SlotSection> secs;    // all three groups; mimi[1]'s bases stay null until that side exists
-    std::vector<uint32_t> sig;        // the blob signature of this configuration
-    int nsec_base = 0, nsec_side = 0; // LM + mimi[0]; one Mimi side
-    unsigned chunks_base = 0, chunks_side = 0;
-    size_t bytes_base = 0, bytes_side = 0;
-    // sections the importer range-checks
-    int sec_lm_idx = -1, sec_text_token = -1, sec_first_step = -1, sec_rng_pos = -1, sec_next_cb = -1, sec_mimi_idx = -1;
-    SlotSection* d_secs = nullptr;
-    bool d_has1 = false;              // the device table holds mimi[1]'s bases
-    char* d_stage = nullptr;
-    size_t d_stage_cap = 0;
-    char* h_stage = nullptr;          // pinned
-    size_t h_stage_cap = 0;
-    int* d_slots = nullptr;
-    int slots_cap = 0;
-    hipEvent_t ev_packed = nullptr;
-  } xfer;
+  // mimi[0], then as the optional group mimi[1] — and the staging buffers (dsm_slot_xfer.inc).  Built by the first call that needs it.
+  SlotXfer xfer;
+  struct {  // sections the importer range-checks
+    int lm_idx = -1, text_token = -1, first_step = -1, rng_pos = -1, next_cb = -1, mimi_idx = -1;
+  } xsec;
 };
 
 // ----------------------------------------------------------------------------------------------

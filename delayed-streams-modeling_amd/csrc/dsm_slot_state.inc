@@ -1,6 +1,7 @@
 // dsm_slot_state.inc — slot snapshots: dsm_asr_export_slots / dsm_asr_import_slots / dsm_asr_move_slots (included by
-// dsm_engine.hip behind dsm_engine_api.inc).  The blob format is csrc/dsm_slot_blob.h; the two kernels are
-// slot_state_pack_kernel / slot_state_unpack_kernel (dsm_kernels.h); DESIGN.md has the table of state.
+// dsm_engine.hip behind dsm_engine_api.inc).  This file is what is STT about them: which sections a slot's state is, the
+// signature, the host items, the payload's index checks and the three calls.  The blob format is csrc/dsm_slot_blob.h; the
+// section table, staging and the pack / unpack launch are csrc/dsm_slot_xfer.inc; DESIGN.md has the table of state.
 //
 // Where a slot's state lives is what reset_transformer_slot, reset_mimi_slot and dsm_asr_reset_slot already enumerate, plus what
 // they leave alone because a fresh value is never read (the ring rows behind pos, the shifted codes behind first_step, the
@@ -8,8 +9,6 @@
 // staging buffers are free again and both host threads' streams see what an import wrote.
 
 namespace {
-
-using SlotXfer = dsm_engine::SlotXfer;
 
 // Sections of one Mimi side, in blob order: ring position, ring index, K and V rows per layer, the carried conv states in
 // ConvStateDesc order.  s null: the side does not exist yet — same sizes (taken from mimi[0]'s table), null bases.
@@ -35,7 +34,7 @@ void slot_mimi_sections(const dsm_engine* e, const MimiState* s, std::vector<Slo
   }
 }
 
-// The section table, its payload offsets and piece counts, and the signature: host work only, once per engine.
+// The section list (its offsets and piece counts: slot_layout_finish) and the signature: host work only, once per engine.
 void slot_layout_build(dsm_engine* e) {
   SlotXfer& x = e->xfer;
   if (!x.secs.empty()) return;
@@ -51,36 +50,21 @@ void slot_layout_build(dsm_engine* e) {
     return (int)v.size() - 1;
   };
   add(s.tr.pos, 4, 4);
-  x.sec_lm_idx = add(s.tr.idx, 4, 4);
-  x.sec_text_token = add(s.text_token, 4, 4);
-  x.sec_first_step = add(s.first_step, 1, 1);
-  x.sec_rng_pos = add(s.rng_pos, 8, 8);
+  e->xsec.lm_idx = add(s.tr.idx, 4, 4);
+  e->xsec.text_token = add(s.text_token, 4, 4);
+  e->xsec.first_step = add(s.first_step, 1, 1);
+  e->xsec.rng_pos = add(s.rng_pos, 8, 8);
   add(s.rng_key, 32, 32);
-  x.sec_next_cb = add(s.next_cb, (size_t)c.audio_codebooks * 4, (size_t)c.audio_codebooks * 4);
+  e->xsec.next_cb = add(s.next_cb, (size_t)c.audio_codebooks * 4, (size_t)c.audio_codebooks * 4);
   const size_t ring = (size_t)c.lm.d_model * c.lm.context * (c.kv_bf16 ? 2 : 4);
   for (int l = 0; l < c.lm.num_layers; ++l) {
     add(s.tr.k[l], ring, ring);
     add(s.tr.v[l], ring, ring);
   }
-  x.sec_mimi_idx = (int)v.size() + 1;
+  e->xsec.mimi_idx = (int)v.size() + 1;
   slot_mimi_sections(e, &e->mimi[0], &v);
-  x.nsec_base = (int)v.size();
+  const int nsec_base = (int)v.size();
   slot_mimi_sections(e, nullptr, &v);
-  x.nsec_side = (int)v.size() - x.nsec_base;
-  long off = 0;
-  unsigned chunk = 0;
-  for (int i = 0; i < (int)v.size(); ++i) {
-    if (i == x.nsec_base) {
-      x.bytes_base = (size_t)off;
-      x.chunks_base = chunk;
-    }
-    v[i].off = off;
-    v[i].chunk0 = chunk;
-    off += (long)dsm_slot_blob::align16((uint64_t)v[i].bytes);
-    chunk += (unsigned)((v[i].bytes + kSlotChunk - 1) / kSlotChunk);
-  }
-  x.bytes_side = (size_t)off - x.bytes_base;
-  x.chunks_side = chunk - x.chunks_base;
   const dsm_transformer_config& mt = c.mimi.transformer;
   x.sig = {(uint32_t)c.lm.num_layers, (uint32_t)c.lm.num_heads, (uint32_t)(c.lm.d_model / c.lm.num_heads), (uint32_t)c.lm.context,
            (uint32_t)(c.kv_bf16 ? 1 : 0), (uint32_t)mt.num_layers, (uint32_t)mt.num_heads, (uint32_t)(mt.d_model / mt.num_heads),
@@ -90,7 +74,7 @@ void slot_layout_build(dsm_engine* e) {
     x.sig.push_back((uint32_t)d.S);
     x.sig.push_back((uint32_t)d.C);
   }
-  x.secs = std::move(v);
+  slot_layout_finish(x, std::move(v), nsec_base);
 }
 
 const char* slot_sig_name(size_t i) {
@@ -101,32 +85,9 @@ const char* slot_sig_name(size_t i) {
   return i < sizeof names / sizeof names[0] ? names[i] : "carried conv state (S, C) list";
 }
 
-// First difference between two signatures, as text; empty when they agree.
-std::string slot_sig_mismatch(const uint32_t* theirs, size_t n_theirs, const std::vector<uint32_t>& ours) {
-  char buf[160];
-  for (size_t i = 0; i < ours.size() && i < n_theirs; ++i)
-    if (theirs[i] != ours[i]) {
-      snprintf(buf, sizeof buf, "%s differs: %u there, %u here", slot_sig_name(i), theirs[i], ours[i]);
-      return buf;
-    }
-  if (n_theirs != ours.size()) {
-    snprintf(buf, sizeof buf, "signature length differs: %zu words there, %zu here", n_theirs, ours.size());
-    return buf;
-  }
-  return std::string();
-}
-
-size_t slot_bytes_of(const SlotXfer& x, bool with1) { return x.bytes_base + (with1 ? x.bytes_side : 0); }
-
-bool slot_xfer_fits(const dsm_engine* e, int n, bool host, bool with1) {
-  const SlotXfer& x = e->xfer;
-  const size_t need = (size_t)n * slot_bytes_of(x, with1);
-  return x.d_secs && x.ev_packed && (!with1 || x.d_has1) && n <= x.slots_cap && need <= x.d_stage_cap && (!host || need <= x.h_stage_cap);
-}
-
-// Device side of the table and the staging buffers, sized for n slots; with keep: the per-slot keep bytes of every Mimi side
-// whose first call has not run.  Called with SlotXfer::mu held and BEFORE the API's shared lock is taken: allocations take the
-// exclusive side, for the reason ensure_model_side_mimi gives.
+// Staging for n slots (slot_stage_ensure), behind what only this engine can do first: the model-side Mimi where the caller
+// wants it; with keep: the per-slot keep bytes of every Mimi side whose first call has not run.  Called with SlotXfer::mu
+// held and BEFORE the API's shared lock is taken: allocations take the exclusive side, for the reason ensure_model_side_mimi gives.
 int slot_xfer_ensure(dsm_engine* e, int n, bool host, bool want_mimi1, bool keep) {
   SlotXfer& x = e->xfer;
   HIPCHK(hipSetDevice(e->device));
@@ -141,83 +102,9 @@ int slot_xfer_ensure(dsm_engine* e, int n, bool host, bool want_mimi1, bool keep
       s.keep_h.assign((size_t)e->B, 0);
       if (int rc = e->dalloc(&s.keep, (size_t)e->B)) return rc;
     }
-  if (slot_xfer_fits(e, n, host, has1)) return 0;
-  if (!x.ev_packed)
-    if (int rc = e->new_event(&x.ev_packed)) return rc;
-  if (!x.d_secs)
-    if (int rc = e->dalloc(&x.d_secs, x.secs.size())) return rc;
-  if (!x.d_has1) {  // first time, or mimi[1] came into being since
-    if (has1) {
-      std::vector<SlotSection> side;
-      slot_mimi_sections(e, &e->mimi[1], &side);
-      for (int i = 0; i < x.nsec_side; ++i) x.secs[(size_t)x.nsec_base + i].base = side[(size_t)i].base;
-    }
-    HIPCHK(hipMemcpy(x.d_secs, x.secs.data(), sizeof(SlotSection) * x.secs.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    x.d_has1 = has1;
-  }
-  if (n > x.slots_cap) {
-    e->dfree(x.d_slots);
-    x.d_slots = nullptr;
-    x.slots_cap = 0;
-    if (int rc = e->dalloc(&x.d_slots, (size_t)n)) return rc;
-    x.slots_cap = n;
-  }
-  const size_t need = (size_t)n * slot_bytes_of(x, has1);
-  if (need > x.d_stage_cap) {
-    e->dfree(x.d_stage);
-    x.d_stage = nullptr;
-    x.d_stage_cap = 0;
-    if (int rc = e->dalloc(&x.d_stage, need, false)) return rc;
-    x.d_stage_cap = need;
-  }
-  if (host && need > x.h_stage_cap) {
-    e->hfree(x.h_stage);
-    x.h_stage = nullptr;
-    x.h_stage_cap = 0;
-    if (int rc = e->halloc(&x.h_stage, need)) return rc;
-    x.h_stage_cap = need;
-  }
-  return 0;
-}
-
-// One launch: the n slots listed at d_slots <-> stage, slot j at stage + j * slot_bytes.  Tables and slot list are `e`'s; the
-// staging buffer may be another engine's (move).  with1: mimi[1]'s sections too.
-int slot_launch(dsm_engine* e, hipStream_t st, bool pack, int n, bool with1, char* stage) {
-  const SlotXfer& x = e->xfer;
-  const int nsec = x.nsec_base + (with1 ? x.nsec_side : 0);
-  const unsigned chunks = x.chunks_base + (with1 ? x.chunks_side : 0);
-  const long slot_bytes = (long)slot_bytes_of(x, with1);
-  // a couple of thousand workgroups in all (eight per CU); each strides over the pieces that are left
-  unsigned gx = 2048u / (unsigned)n;
-  if (gx < 1) gx = 1;
-  if (gx > chunks) gx = chunks;
-  if (pack)
-    hipLaunchKernelGGL(slot_state_pack_kernel, dim3(gx, (unsigned)n), dim3(256), 0, st, (const SlotSection*)x.d_secs, nsec, chunks,
-                       (const int*)x.d_slots, stage, slot_bytes);
-  else
-    hipLaunchKernelGGL(slot_state_unpack_kernel, dim3(gx, (unsigned)n), dim3(256), 0, st, (const SlotSection*)x.d_secs, nsec, chunks,
-                       (const int*)x.d_slots, stage, slot_bytes);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int slot_check_list(dsm_engine* e, const int* slots, int n, bool distinct, const char* what) {
-  if (!slots || n < 1) { e->set_error("%s: empty slot list", what); return DSM_ERR_INVALID; }
-  if (n > e->B) { e->set_error("%s: %d slots listed, the engine has %d", what, n, e->B); return DSM_ERR_INVALID; }
-  for (int i = 0; i < n; ++i)
-    if (slots[i] < 0 || slots[i] >= e->B) {
-      e->set_error("%s: batch index out of range: %d >= %d", what, slots[i], e->B);
-      return DSM_ERR_INVALID;
-    }
-  if (distinct) {
-    std::vector<uint8_t> seen((size_t)e->B, 0);
-    for (int i = 0; i < n; ++i) {
-      if (seen[(size_t)slots[i]]) { e->set_error("%s: slot %d is listed twice", what, slots[i]); return DSM_ERR_INVALID; }
-      seen[(size_t)slots[i]] = 1;
-    }
-  }
-  return 0;
+  std::vector<SlotSection> side1;  // mimi[1] came into being since the table went to the device: its bases
+  if (has1 && !x.d_has_opt) slot_mimi_sections(e, &e->mimi[1], &side1);
+  return slot_stage_ensure(e, x, n, host, has1, side1);
 }
 
 // The host half of the listed slots, with the per-side "first call has not run and nothing was imported" flags.
@@ -274,19 +161,19 @@ int slot_payload_check(dsm_engine* e, const uint8_t* payload, int n, bool has1) 
   for (int i = 0; i < n; ++i) {
     const uint8_t* p = payload + (size_t)i * sb;
     auto at = [&](int sec) { return p + x.secs[(size_t)sec].off; };
-    const uint32_t idx = rd32(at(x.sec_lm_idx));
+    const uint32_t idx = rd32(at(e->xsec.lm_idx));
     if (idx >= (uint32_t)c.lm.context) { e->set_error("slot blob: slot %d: LM ring index %u >= context %d", i, idx, c.lm.context); return DSM_ERR_INVALID; }
-    const uint32_t tt = rd32(at(x.sec_text_token));
+    const uint32_t tt = rd32(at(e->xsec.text_token));
     if (tt >= (uint32_t)c.text_in_vocab_size) { e->set_error("slot blob: slot %d: text token %u >= text_in_vocab_size %d", i, tt, c.text_in_vocab_size); return DSM_ERR_INVALID; }
-    if (*at(x.sec_first_step) > 1) { e->set_error("slot blob: slot %d: first_step is not 0 or 1", i); return DSM_ERR_INVALID; }
-    const uint64_t rp = rd64(at(x.sec_rng_pos));
+    if (*at(e->xsec.first_step) > 1) { e->set_error("slot blob: slot %d: first_step is not 0 or 1", i); return DSM_ERR_INVALID; }
+    const uint64_t rp = rd64(at(e->xsec.rng_pos));
     if (rp % 16) { e->set_error("slot blob: slot %d: Gumbel stream position %llu is not a multiple of 16", i, (unsigned long long)rp); return DSM_ERR_INVALID; }
     for (int q = 0; q < c.audio_codebooks; ++q) {
-      const uint32_t code = rd32(at(x.sec_next_cb) + 4 * q);
+      const uint32_t code = rd32(at(e->xsec.next_cb) + 4 * q);
       if (code >= (uint32_t)c.audio_vocab_size) { e->set_error("slot blob: slot %d: carried audio code %u >= audio_vocab_size %d", i, code, c.audio_vocab_size); return DSM_ERR_INVALID; }
     }
     for (int side = 0; side < (has1 ? 2 : 1); ++side) {
-      const uint32_t mi = rd32(at(x.sec_mimi_idx + side * x.nsec_side));
+      const uint32_t mi = rd32(at(e->xsec.mimi_idx + side * x.nsec_opt));
       if (mi >= (uint32_t)c.mimi.transformer.context) {
         e->set_error("slot blob: slot %d: Mimi side %d ring index %u >= context %d", i, side, mi, c.mimi.transformer.context);
         return DSM_ERR_INVALID;
@@ -308,7 +195,7 @@ bool slot_ticket_outstanding(dsm_engine* e) {
 int slot_move_pack(dsm_engine* e, const int* slots, int n, bool has1, std::vector<dsm_slot_blob::HostItem>* items) {
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
-  if (!slot_xfer_fits(e, n, false, has1) || has1 != e->mimi1_ready.load(std::memory_order_acquire)) {
+  if (!slot_xfer_fits(e->xfer, n, false, has1) || has1 != e->mimi1_ready.load(std::memory_order_acquire)) {
     e->set_error("move_slots: the engine's model-side Mimi came into being during the call; call again");
     return DSM_ERR_STATE;
   }
@@ -317,7 +204,7 @@ int slot_move_pack(dsm_engine* e, const int* slots, int n, bool has1, std::vecto
   slot_gather_items(e, slots, n, has1, items);
   SlotXfer& x = e->xfer;
   HIPCHK(hipMemcpyAsync(x.d_slots, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, e->s_model));
-  if (int rc = slot_launch(e, e->s_model, true, n, has1, x.d_stage)) return rc;
+  if (int rc = slot_launch(e, x, e->s_model, true, n, has1, x.d_stage)) return rc;
   HIPCHK(hipEventRecord(x.ev_packed, e->s_model));
   return 0;
 }
@@ -327,13 +214,13 @@ int slot_move_unpack(dsm_engine* e, const int* slots, int n, bool has1, char* st
                      const std::vector<dsm_slot_blob::HostItem>& items) {
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
-  if (!slot_xfer_fits(e, n, false, has1)) { e->set_error("move_slots: destination staging not ready"); return DSM_ERR_STATE; }
+  if (!slot_xfer_fits(e->xfer, n, false, has1)) { e->set_error("move_slots: destination staging not ready"); return DSM_ERR_STATE; }
   if (int rc = dsm_sync(e)) return rc;
   SlotXfer& x = e->xfer;
   hipStream_t st = e->s_model;
   HIPCHK(hipStreamWaitEvent(st, packed, 0));
   HIPCHK(hipMemcpyAsync(x.d_slots, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-  if (int rc = slot_launch(e, st, false, n, has1, stage)) return rc;
+  if (int rc = slot_launch(e, x, st, false, n, has1, stage)) return rc;
   if (int rc = slot_apply_items(e, st, slots, n, has1, items)) return rc;
   HIPCHK(hipStreamSynchronize(st));
   return 0;
@@ -352,7 +239,7 @@ int dsm_slot_blob_info(const void* buf, size_t len, struct dsm_slot_blob_info* o
 
 int dsm_asr_export_slots(dsm_engine* e, const int* slots, int n, void* buf, size_t cap, size_t* needed) {
   if (!e) return DSM_ERR_INVALID;
-  if (int rc = slot_check_list(e, slots, n, false, "export_slots")) return rc;
+  if (int rc = slot_check_list(e, e->B, slots, n, false, "export_slots")) return rc;
   SlotXfer& x = e->xfer;
   std::lock_guard<std::mutex> one(x.mu);
   slot_layout_build(e);
@@ -374,34 +261,27 @@ int dsm_asr_export_slots(dsm_engine* e, const int* slots, int n, void* buf, size
   if (needed) *needed = total;
   if (!buf) return 0;
   if (cap < total) { e->set_error("export_slots: buffer of %zu bytes, the blob needs %zu", cap, total); return DSM_ERR_INVALID; }
-  if (!slot_xfer_fits(e, n, true, has1)) {
+  if (!slot_xfer_fits(e->xfer, n, true, has1)) {
     e->set_error("export_slots: the engine's model-side Mimi came into being during the call; call again");
     return DSM_ERR_STATE;
   }
   if (int rc = dsm_sync(e)) return rc;  // both streams and every group: the state is what the last finished step left
   hipStream_t st = e->s_model;
   HIPCHK(hipMemcpyAsync(x.d_slots, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-  if (int rc = slot_launch(e, st, true, n, has1, x.d_stage)) return rc;
+  if (int rc = slot_launch(e, x, st, true, n, has1, x.d_stage)) return rc;
   HIPCHK(hipMemcpyAsync(x.h_stage, x.d_stage, (size_t)n * sb, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   uint8_t* out = static_cast<uint8_t*>(buf);
   memcpy(out, front.data(), front.size());
   uint8_t* payload = out + front.size();
   memcpy(payload, x.h_stage, (size_t)n * sb);
-  // the gaps behind sections that are no multiple of 16 were not written by the kernel: defined bytes in the blob
-  const int nsec = x.nsec_base + (has1 ? x.nsec_side : 0);
-  for (int i = 0; i < n; ++i)
-    for (int s = 0; s < nsec; ++s) {
-      const SlotSection& sec = x.secs[(size_t)s];
-      const size_t gap = (size_t)dsm_slot_blob::align16((uint64_t)sec.bytes) - (size_t)sec.bytes;
-      if (gap) memset(payload + (size_t)i * sb + (size_t)sec.off + (size_t)sec.bytes, 0, gap);
-    }
+  slot_zero_gaps(x, payload, n, has1);
   return 0;
 }
 
 int dsm_asr_import_slots(dsm_engine* e, const int* slots, int n, const void* buf, size_t len) {
   if (!e) return DSM_ERR_INVALID;
-  if (int rc = slot_check_list(e, slots, n, true, "import_slots")) return rc;
+  if (int rc = slot_check_list(e, e->B, slots, n, true, "import_slots")) return rc;
   SlotXfer& x = e->xfer;
   std::lock_guard<std::mutex> one(x.mu);
   slot_layout_build(e);
@@ -414,7 +294,7 @@ int dsm_asr_import_slots(dsm_engine* e, const int* slots, int n, const void* buf
   {
     std::vector<uint32_t> theirs(h.sig_words);
     if (h.sig_words) memcpy(theirs.data(), p + h.sig_offset(), 4 * (size_t)h.sig_words);
-    const std::string diff = slot_sig_mismatch(theirs.data(), theirs.size(), x.sig);
+    const std::string diff = slot_sig_mismatch(theirs.data(), theirs.size(), x.sig, slot_sig_name);
     if (!diff.empty()) { e->set_error("import_slots: the blob is of another configuration: %s", diff.c_str()); return DSM_ERR_INVALID; }
   }
   std::vector<dsm_slot_blob::HostItem> items;
@@ -431,13 +311,13 @@ int dsm_asr_import_slots(dsm_engine* e, const int* slots, int n, const void* buf
   if (int rc = slot_xfer_ensure(e, n, true, has1, true)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
-  if (!slot_xfer_fits(e, n, true, has1)) { e->set_error("import_slots: staging not ready"); return DSM_ERR_STATE; }
+  if (!slot_xfer_fits(e->xfer, n, true, has1)) { e->set_error("import_slots: staging not ready"); return DSM_ERR_STATE; }
   if (int rc = dsm_sync(e)) return rc;
   hipStream_t st = e->s_model;
   memcpy(x.h_stage, payload, (size_t)n * sb);
   HIPCHK(hipMemcpyAsync(x.d_stage, x.h_stage, (size_t)n * sb, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(x.d_slots, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-  if (int rc = slot_launch(e, st, false, n, has1, x.d_stage)) return rc;
+  if (int rc = slot_launch(e, x, st, false, n, has1, x.d_stage)) return rc;
   if (int rc = slot_apply_items(e, st, slots, n, has1, items)) return rc;
   HIPCHK(hipStreamSynchronize(st));  // the encoder stream and the groups start behind this
   return 0;
@@ -445,8 +325,8 @@ int dsm_asr_import_slots(dsm_engine* e, const int* slots, int n, const void* buf
 
 int dsm_asr_move_slots(dsm_engine* src, const int* src_slots, dsm_engine* dst, const int* dst_slots, int n) {
   if (!src || !dst) return DSM_ERR_INVALID;
-  if (int rc = slot_check_list(src, src_slots, n, false, "move_slots (source)")) return rc;
-  if (int rc = slot_check_list(dst, dst_slots, n, true, "move_slots (destination)")) { src->set_error("%s", dst->err.c_str()); return rc; }
+  if (int rc = slot_check_list(src, src->B, src_slots, n, false, "move_slots (source)")) return rc;
+  if (int rc = slot_check_list(dst, dst->B, dst_slots, n, true, "move_slots (destination)")) { src->set_error("%s", dst->err.c_str()); return rc; }
   if (src == dst)
     for (int i = 0; i < n; ++i)
       for (int j = 0; j < n; ++j)
@@ -463,7 +343,7 @@ int dsm_asr_move_slots(dsm_engine* src, const int* src_slots, dsm_engine* dst, c
   slot_layout_build(src);
   slot_layout_build(dst);
   {
-    const std::string diff = slot_sig_mismatch(src->xfer.sig.data(), src->xfer.sig.size(), dst->xfer.sig);
+    const std::string diff = slot_sig_mismatch(src->xfer.sig.data(), src->xfer.sig.size(), dst->xfer.sig, slot_sig_name);
     if (!diff.empty()) { src->set_error("move_slots: the engines differ in configuration: %s", diff.c_str()); return DSM_ERR_INVALID; }
   }
   const bool has1 = src->mimi1_ready.load(std::memory_order_acquire);

@@ -1,5 +1,5 @@
 // dsm_tts_slot_state.inc — the TTS slot blob's entry point (included by dsm_engine.hip behind dsm_tts_voice.inc).  The format,
-// its writer and its checked reader are csrc/dsm_tts_slot_blob.h, host only; DESIGN.md section 7.2 has the table of state the
+// its writer and its checked reader are csrc/dsm_tts_slot_blob.h over the container of csrc/dsm_slot_blob.h, host only; DESIGN.md section 7.2 has the table of state the
 // blob is laid out for.  The engine calls that fill and consume a blob (export / import) are not in the library yet.
 
 extern "C" {
