@@ -158,7 +158,11 @@ ABI_SYMBOLS = [
     "dsm_spm_encode", "dsm_spm_decode", "dsm_worker_set_tokenizer_file",
     "dsm_tts_attach_tokenizer", "dsm_tts_request_push_text", "dsm_tts_word_text",
     "dsm_tts_slot_blob_info",
+    "dsm_asr_set_token_scores", "dsm_asr_token_scores", "dsm_asr_token_scores_dev", "dsm_asr_poll_word_scores",
+    "dsm_token_scores_host", "dsm_debug_token_scores", "dsm_worker_set_word_scores",
 ]
+SCORES_MAX_TOP = 8  # DSM_SCORES_MAX_TOP
+SCORES_NONE = 0xFFFFFFFF  # the id of a top-N entry beyond the vocabulary
 TTS_COND_LUT, TTS_COND_CONTINUOUS = 0, 1  # DSM_TTS_COND_*
 TTS_RUN_MAX = 16  # DSM_TTS_RUN_MAX
 TTS_REQ_IDLE, TTS_REQ_RUNNING, TTS_REQ_WAITING, TTS_REQ_DONE, TTS_REQ_DONE_LIMIT = range(5)  # DSM_TTS_REQ_*
@@ -367,6 +371,16 @@ def load_library(path=None):
     lib.dsm_tts_word_text.restype = C.c_int64
     lib.dsm_tts_slot_blob_info.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(TtsSlotBlobInfo)]
     lib.dsm_tts_slot_blob_info.restype = C.c_int
+    lib.dsm_asr_set_token_scores.argtypes = [vp, C.c_int]
+    lib.dsm_asr_token_scores.argtypes = [vp, fp, u32p, fp]
+    lib.dsm_asr_token_scores_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.dsm_asr_poll_word_scores.argtypes = [vp, fp, C.c_int]
+    lib.dsm_token_scores_host.argtypes = [fp, C.c_int, C.c_uint32, C.c_int, fp, u32p, fp]
+    lib.dsm_debug_token_scores.argtypes = [vp, fp, C.c_int, C.c_int, u32p, C.c_int, fp, u32p, fp]
+    lib.dsm_worker_set_word_scores.argtypes = [vp, C.c_int]
+    for name in ("dsm_asr_set_token_scores", "dsm_asr_token_scores", "dsm_asr_token_scores_dev", "dsm_asr_poll_word_scores",
+                 "dsm_token_scores_host", "dsm_debug_token_scores", "dsm_worker_set_word_scores"):
+        getattr(lib, name).restype = C.c_int
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
         getattr(lib, name).restype = C.c_int
@@ -486,6 +500,25 @@ def slot_blob_info(blob):
 def tts_slot_blob_info(blob):
     """dsm_tts_slot_blob_info: header fields of a TTS slot blob as a dict (host only, no device); DsmError for a malformed one."""
     return _blob_info(blob, TtsSlotBlobInfo(), "dsm_tts_slot_blob_info", "dsm_tts_last_error")
+
+
+def token_scores_host(logits, token, top_n=0):
+    """dsm_token_scores_host: (logprob of `token`, top ids [top_n] uint32, top logprobs [top_n] float32) of one row of f32
+    logits, by the definition of csrc/dsm_token_scores.h computed serially on the host.  No device needed."""
+    lib = load_library()
+    row = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    lp = np.zeros(1, dtype=np.float32)
+    n = max(int(top_n), 0)
+    ids, lps = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float32)
+    token = int(token)
+    if not 0 <= token < 2 ** 32:
+        raise DsmError("token_scores_host: token outside uint32")
+    rc = lib.dsm_token_scores_host(_ptr(row), row.size, token, int(top_n), _ptr(lp), _ptr(ids) if n else None, _ptr(lps) if n else None)
+    if rc < 0:
+        e = DsmError(f"dsm_token_scores_host: error {rc}")
+        e.code = rc
+        raise e
+    return lp[0], ids, lps
 
 
 def _ptr(a):
@@ -666,6 +699,15 @@ class Worker:
 
     def set_tokenizer_file(self, path):
         rc = self.lib.dsm_worker_set_tokenizer_file(self.h, os.fsencode(path))
+        if rc < 0:
+            e = DsmError(f"dsm error {rc}: {self._err()}")
+            e.code = rc
+            raise e
+
+    def set_word_scores(self, on):
+        """dsm_worker_set_word_scores: Word messages carry logprob / min_logprob (mean and minimum of the word's token
+        log-probabilities).  Engine-backed workers only."""
+        rc = self.lib.dsm_worker_set_word_scores(self.h, 1 if on else 0)
         if rc < 0:
             e = DsmError(f"dsm error {rc}: {self._err()}")
             e.code = rc
@@ -959,6 +1001,57 @@ class AsrEngine:
             else:
                 out.append(("Step", m.step_idx))
         return out
+
+    # token scores (include/dsm.h "token scores")
+    def set_token_scores(self, top_n):
+        """-1 (or None): off, the default.  0..8: every step also yields the log-probability of each slot's text token and
+        the top_n best entries of its logits row."""
+        self._check(self.lib.dsm_asr_set_token_scores(self.h, -1 if top_n is None else int(top_n)))
+
+    def token_scores(self):
+        """Scores of the last step_tokens / step_pcm / step_tokens_ticket: (logprob [B] f32, top_ids [B, top_n] u32,
+        top_logprobs [B, top_n] f32)."""
+        lp = np.zeros(self.B, dtype=np.float32)
+        ids = np.zeros((self.B, SCORES_MAX_TOP), dtype=np.uint32)
+        lps = np.zeros((self.B, SCORES_MAX_TOP), dtype=np.float32)
+        n = self._check(self.lib.dsm_asr_token_scores(self.h, _ptr(lp), _ptr(ids), _ptr(lps)))
+        # the library wrote [B][top_n] densely into the front of the two buffers
+        return lp, ids.reshape(-1)[:self.B * n].reshape(self.B, n).copy(), lps.reshape(-1)[:self.B * n].reshape(self.B, n).copy()
+
+    def token_scores_dev(self):
+        """(top_n, device pointers of logprob [B], top_ids [B, 8], top_logprobs [B, 8]) for the *_dev callers: valid after
+        sync(), overwritten by the next step."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = self._check(self.lib.dsm_asr_token_scores_dev(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return n, a.value, b.value, c.value
+
+    def poll_word_scores(self, cap=4096 * 8):
+        """Parallel to poll_msgs' tokens: float32 array whose entries [tokens_offset, tokens_offset + n_tokens) are a Word's
+        token log-probabilities (NaN = not recorded).  Use word_scores() for them per message."""
+        out = np.zeros(cap, dtype=np.float32)
+        n = self._check(self.lib.dsm_asr_poll_word_scores(self.h, _ptr(out), cap))
+        return out[:n]
+
+    def word_scores(self, cap=4096):
+        """[(batch_idx, [logprob of each token]), ...] for the Word messages of the last step, in poll_msgs order."""
+        msgs = (AsrMsg * cap)()
+        n = self._check(self.lib.dsm_asr_poll_msgs(self.h, msgs, cap, None, 0))
+        lps = self.poll_word_scores(cap * 8)
+        return [(msgs[i].batch_idx, lps[msgs[i].tokens_offset:msgs[i].tokens_offset + msgs[i].n_tokens].copy())
+                for i in range(n) if msgs[i].kind == MSG_WORD]
+
+    def debug_token_scores(self, logits, tokens, top_n):
+        """Test aid: the step's score KERNEL on caller-supplied rows.  logits [n, V] f32, tokens [n] -> (logprob [n],
+        top_ids [n, top_n], top_logprobs [n, top_n])."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        n, V = logits.shape
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32).reshape(n)
+        k = int(top_n)
+        lp = np.zeros(n, dtype=np.float32)
+        ids, lps = np.zeros((n, max(k, 0)), dtype=np.uint32), np.zeros((n, max(k, 0)), dtype=np.float32)
+        self._check(self.lib.dsm_debug_token_scores(self.h, _ptr(logits), n, V, _ptr(tokens), k, _ptr(lp),
+                                                    _ptr(ids) if k > 0 else None, _ptr(lps) if k > 0 else None))
+        return lp, ids, lps
 
     def reset_batch_idx(self, slot):
         self._check(self.lib.dsm_asr_reset_slot(self.h, slot))

@@ -247,6 +247,7 @@ struct LmState {
 struct HostItem {  // ItemState — core/asr.rs:15-51 (word assembly stays on the host)
   size_t step_idx = 0;
   std::vector<uint32_t> word_tokens;
+  std::vector<float> word_logprobs;  // one per word token (dsm_asr_set_token_scores); NaN = not recorded (scores off, or an imported word)
   bool unended_word = false;
   double last_stop_time = 0.0;
 };
@@ -287,6 +288,14 @@ struct dsm_engine : DsmDevice {
   size_t model_step_idx = 0;
   std::vector<dsm_asr_msg> msgs;
   std::vector<uint32_t> msg_tokens;
+  std::vector<float> msg_logprobs;  // moves in step with msg_tokens (dsm_asr_poll_word_scores)
+  // token scores (dsm_asr_set_token_scores; dsm_token_scores.h): -1 off, else the top_n of lm_token_scores_kernel, which then
+  // runs behind each group's argmax.  Device buffers [B], [B][DSM_SCORES_MAX_TOP] x 2 and their pinned mirrors, allocated by the
+  // first call that turns scores on; scores_host_steps counts the host-pointer steps since the setting last changed.
+  int scores_top_n = -1;
+  float *scores_lp = nullptr, *scores_top_lp = nullptr, *h_scores_lp = nullptr, *h_scores_top_lp = nullptr;
+  uint32_t *scores_top_id = nullptr, *h_scores_top_id = nullptr;
+  size_t scores_host_steps = 0;
   dsm_metrics metrics{};
   // run-ahead pipeline between the encoder thread and the model thread (dsm_mimi_encode_step_async /
   // dsm_asr_step_tokens_ticket): the reference's sync_channel(100) of PipelineMsg (srv/batched_asr.rs:291), here a ring of

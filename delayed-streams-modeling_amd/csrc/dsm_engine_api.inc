@@ -452,6 +452,17 @@ int mimi_decode_body(DsmDevice* e, const MimiW& w, MimiDecState& s, int B, hipSt
   return 0;
 }
 
+// lm_token_scores_kernel over `rows` rows of V logits: staged in LDS while a row fits, read from L2 pass by pass beyond that
+int launch_token_scores(DsmDevice* e, hipStream_t st, int rows, const float* logits, int V, const uint32_t* tokens, int top_n, float* lp,
+                        uint32_t* top_id, float* top_lp) {
+  if (V <= DSM_SCORES_STAGE_MAX)
+    hipLaunchKernelGGL(lm_token_scores_kernel<true>, dim3(rows), dim3(256), sizeof(float) * (size_t)V, st, logits, V, tokens, top_n, lp, top_id, top_lp);
+  else
+    hipLaunchKernelGGL(lm_token_scores_kernel<false>, dim3(rows), dim3(256), 0, st, logits, V, tokens, top_n, lp, top_id, top_lp);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // asr::State::step_tokens device part — core/asr.rs:165-217, for the slots [b0, b0+nb) of one stream group.
 // Part 1 (eager, three launches): the group's private mask copy, token shift + pad select + embedding sum, next_codebooks
 // update; it ends with the event that tells the model stream the step's shared inputs (codes, mask) are consumed.
@@ -485,6 +496,11 @@ int lm_group_body(dsm_engine* e, hipStream_t st, int g, uint32_t* d_text_out, fl
     hipLaunchKernelGGL(lm_argmax_kernel, dim3(nb), dim3(256), 0, st, logits, c.text_out_vocab_size, d_text_out + b0,
                        s.text_token + b0, s.first_step + b0, gmask);
   HIPCHK(hipGetLastError());
+  if (e->scores_top_n >= 0) {  // dsm_asr_set_token_scores: always from the raw logits, whichever kernel picked the token
+    if ((rc = launch_token_scores(e, st, nb, logits, c.text_out_vocab_size, d_text_out + b0, e->scores_top_n, e->scores_lp + b0,
+                                  e->scores_top_id + (size_t)b0 * DSM_SCORES_MAX_TOP, e->scores_top_lp + (size_t)b0 * DSM_SCORES_MAX_TOP)))
+      return rc;
+  }
   if (c.extra_heads_num > 0 && d_prs_out) {
     const int ehw = c.extra_heads_num * c.extra_heads_dim;
     float* eh = s.eh + (size_t)b0 * ehw;
@@ -522,10 +538,11 @@ int lm_group_head(dsm_engine* e, hipStream_t st, int g, const uint32_t* d_codes,
 }
 
 // Rest of the group's step: one hipGraph once settled.  Capture key: the stream's workspace slot, the caller's output
-// pointers (everything else is engine-owned) and whether the head already ran the transformer's prefix.
+// pointers (everything else is engine-owned), whether the head already ran the transformer's prefix, and the token-scores
+// setting (off adds nothing to the key; each top_n is a body of its own, since it is a launch argument).
 int lm_group_rest(dsm_engine* e, hipStream_t st, int g, uint32_t* d_text_out, float* d_prs_out, bool after_prefix) {
   const uint64_t key = (uint64_t)e->sid(st) ^ ((uint64_t)(uintptr_t)d_text_out << 3) ^ ((uint64_t)(uintptr_t)d_prs_out * 0x9E3779B97F4A7C15ull) ^
-                       (after_prefix ? 0x8000000000000000ull : 0ull);
+                       (after_prefix ? 0x8000000000000000ull : 0ull) ^ ((uint64_t)(e->scores_top_n + 1) * 0xD6E8FEB86659FD93ull);
   return run_captured(e, *e->g_grp[g], st, key, [&] { return lm_group_body(e, st, g, d_text_out, d_prs_out, after_prefix ? 2 : 0); });
 }
 
@@ -578,20 +595,23 @@ int upload_pcm(dsm_engine* e, int side, hipStream_t st, const float* src, hipMem
   return 0;
 }
 
-void push_msg(dsm_engine* e, dsm_asr_msg m, const std::vector<uint32_t>* toks) {
+void push_msg(dsm_engine* e, dsm_asr_msg m, const std::vector<uint32_t>* toks, const std::vector<float>* lps = nullptr) {
   if (m.kind == DSM_MSG_WORD && toks) {
     m.tokens_offset = (int)e->msg_tokens.size();
     m.n_tokens = (int)toks->size();
     e->msg_tokens.insert(e->msg_tokens.end(), toks->begin(), toks->end());
+    e->msg_logprobs.insert(e->msg_logprobs.end(), lps->begin(), lps->end());
   }
   e->msgs.push_back(m);
 }
 
 // host half of step_tokens: word assembly — core/asr.rs:218-252
-void assemble_words(dsm_engine* e, const uint32_t* text_tokens, const uint8_t* mask) {
+// logprobs: the step's token scores [B], or null while they are off (the tokens then carry NaN, "not recorded")
+void assemble_words(dsm_engine* e, const uint32_t* text_tokens, const uint8_t* mask, const float* logprobs) {
   const dsm_asr_config& c = e->cfg;
   e->msgs.clear();
   e->msg_tokens.clear();
+  e->msg_logprobs.clear();
   e->model_step_idx += 1;
   if (c.extra_heads_num > 0) {
     dsm_asr_msg m;
@@ -613,12 +633,14 @@ void assemble_words(dsm_engine* e, const uint32_t* text_tokens, const uint8_t* m
           m.kind = DSM_MSG_WORD;
           m.batch_idx = b;
           m.time = it.last_stop_time;
-          push_msg(e, m, &it.word_tokens);
+          push_msg(e, m, &it.word_tokens, &it.word_logprobs);
           it.word_tokens.clear();
+          it.word_logprobs.clear();
           it.unended_word = true;
         }
       } else {
         it.word_tokens.push_back(text_token);
+        it.word_logprobs.push_back(logprobs ? logprobs[b] : dsm_u32_as_f32(0x7FC00000u));
       }
       if (text_token == 0) {
         double stop_time = (double)(it.step_idx - (size_t)c.asr_delay_in_tokens) / 12.5;
@@ -1095,13 +1117,23 @@ static int step_tokens_host(dsm_engine* e, const uint32_t* d_codes, const uint8_
   HIPCHK(hipMemcpyAsync(e->h_text, s.text_out, sizeof(uint32_t) * (size_t)e->B, hipMemcpyDeviceToHost, e->s_model));
   if (nh > 0)
     HIPCHK(hipMemcpyAsync(e->h_prs, s.prs, sizeof(float) * (size_t)e->B * nh, hipMemcpyDeviceToHost, e->s_model));
+  const int top_n = e->scores_top_n;
+  if (top_n >= 0) {
+    HIPCHK(hipMemcpyAsync(e->h_scores_lp, e->scores_lp, sizeof(float) * (size_t)e->B, hipMemcpyDeviceToHost, e->s_model));
+    if (top_n > 0) {
+      const size_t n = (size_t)e->B * DSM_SCORES_MAX_TOP;
+      HIPCHK(hipMemcpyAsync(e->h_scores_top_id, e->scores_top_id, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, e->s_model));
+      HIPCHK(hipMemcpyAsync(e->h_scores_top_lp, e->scores_top_lp, sizeof(float) * n, hipMemcpyDeviceToHost, e->s_model));
+    }
+  }
   HIPCHK(hipStreamSynchronize(e->s_model));
+  if (top_n >= 0) e->scores_host_steps += 1;
   float ms = 0;
   if (hipEventElapsedTime(&ms, e->ev_c, e->ev_d) == hipSuccess) e->metrics.last_lm_us = ms * 1000.0;
   e->metrics.steps_lm += 1;
   if (text_tokens_out) memcpy(text_tokens_out, e->h_text, sizeof(uint32_t) * (size_t)e->B);
   if (vad_prs_out && nh > 0) memcpy(vad_prs_out, e->h_prs, sizeof(float) * (size_t)e->B * nh);
-  assemble_words(e, e->h_text, mask);
+  assemble_words(e, e->h_text, mask, top_n >= 0 ? e->h_scores_lp : nullptr);
   return 0;
 }
 
@@ -1268,6 +1300,116 @@ int dsm_asr_poll_msgs(dsm_engine* e, dsm_asr_msg* msgs, int cap, uint32_t* token
   int nt = (int)e->msg_tokens.size() < tokens_cap ? (int)e->msg_tokens.size() : tokens_cap;
   if (tokens_out && nt > 0) memcpy(tokens_out, e->msg_tokens.data(), sizeof(uint32_t) * (size_t)nt);
   return n;
+}
+
+// ---- token scores (dsm_token_scores.h) ----
+int dsm_asr_set_token_scores(dsm_engine* e, int top_n) {
+  if (!e) return DSM_ERR_INVALID;
+  if (top_n < -1 || top_n > DSM_SCORES_MAX_TOP) {
+    e->set_error("token scores: top_n must be -1 (off) or 0..%d, got %d", DSM_SCORES_MAX_TOP, top_n);
+    return DSM_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  std::unique_lock<std::shared_mutex> alone(e->api_mu);  // between steps; the allocation (null-stream fill) must not run beside a capture
+  if (top_n >= 0 && !e->scores_lp) {
+    const size_t B = (size_t)e->B, n = B * DSM_SCORES_MAX_TOP;
+    if (int rc = e->dalloc(&e->scores_top_id, n)) return rc;
+    if (int rc = e->dalloc(&e->scores_top_lp, n)) return rc;
+    if (int rc = e->halloc(&e->h_scores_lp, B)) return rc;
+    if (int rc = e->halloc(&e->h_scores_top_id, n)) return rc;
+    if (int rc = e->halloc(&e->h_scores_top_lp, n)) return rc;
+    if (int rc = e->dalloc(&e->scores_lp, B)) return rc;  // last: the test above reads it
+  }
+  if (top_n != e->scores_top_n) e->scores_host_steps = 0;
+  e->scores_top_n = top_n;
+  return 0;
+}
+
+static int scores_on(dsm_engine* e) {
+  if (e->scores_top_n >= 0) return 0;
+  e->set_error("token scores are off: dsm_asr_set_token_scores turns them on");
+  return DSM_ERR_STATE;
+}
+
+int dsm_asr_token_scores(dsm_engine* e, float* logprob_out, uint32_t* top_ids_out, float* top_logprobs_out) {
+  if (!e || !logprob_out) return DSM_ERR_INVALID;
+  if (int rc = scores_on(e)) return rc;
+  if (e->scores_host_steps == 0) {
+    e->set_error("token scores: no dsm_asr_step_tokens / _step_pcm / _step_tokens_ticket since the setting last changed");
+    return DSM_ERR_STATE;
+  }
+  const int top_n = e->scores_top_n;
+  memcpy(logprob_out, e->h_scores_lp, sizeof(float) * (size_t)e->B);
+  for (int b = 0; b < e->B && top_n > 0; ++b) {
+    if (top_ids_out) memcpy(top_ids_out + (size_t)b * top_n, e->h_scores_top_id + (size_t)b * DSM_SCORES_MAX_TOP, sizeof(uint32_t) * (size_t)top_n);
+    if (top_logprobs_out) memcpy(top_logprobs_out + (size_t)b * top_n, e->h_scores_top_lp + (size_t)b * DSM_SCORES_MAX_TOP, sizeof(float) * (size_t)top_n);
+  }
+  return top_n;
+}
+
+int dsm_asr_token_scores_dev(dsm_engine* e, const float** d_logprob, const uint32_t** d_top_ids, const float** d_top_logprobs) {
+  if (!e) return DSM_ERR_INVALID;
+  if (int rc = scores_on(e)) return rc;
+  if (d_logprob) *d_logprob = e->scores_lp;
+  if (d_top_ids) *d_top_ids = e->scores_top_id;
+  if (d_top_logprobs) *d_top_logprobs = e->scores_top_lp;
+  return e->scores_top_n;
+}
+
+int dsm_asr_poll_word_scores(dsm_engine* e, float* logprobs_out, int cap) {
+  if (!e || (!logprobs_out && cap > 0)) return DSM_ERR_INVALID;
+  if (int rc = scores_on(e)) return rc;
+  const int n = (int)e->msg_logprobs.size() < cap ? (int)e->msg_logprobs.size() : cap;
+  if (n > 0) memcpy(logprobs_out, e->msg_logprobs.data(), sizeof(float) * (size_t)n);
+  return n;
+}
+
+int dsm_token_scores_host(const float* logits, int V, uint32_t token, int top_n, float* logprob, uint32_t* top_ids, float* top_logprobs) {
+  if (!logits || !logprob || V < 1 || token >= (uint32_t)V || top_n < 0 || top_n > DSM_SCORES_MAX_TOP ||
+      (top_n > 0 && (!top_ids || !top_logprobs)))
+    return DSM_ERR_INVALID;
+  dsm_token_scores_row(logits, V, token, top_n, logprob, top_ids, top_logprobs);
+  return 0;
+}
+
+int dsm_debug_token_scores(dsm_engine* e, const float* logits, int n, int V, const uint32_t* tokens, int top_n, float* logprob_out,
+                           uint32_t* top_ids_out, float* top_logprobs_out) {
+  if (!e || !logits || !tokens || !logprob_out || n < 1 || V < 1 || V > (1 << 30) || top_n < 0 || top_n > DSM_SCORES_MAX_TOP ||
+      (top_n > 0 && (!top_ids_out || !top_logprobs_out)))
+    return DSM_ERR_INVALID;  // (V beyond 2^30: the kernel's int indices walk a row 2048 entries at a time)
+  for (int i = 0; i < n; ++i)
+    if (tokens[i] >= (uint32_t)V) { e->set_error("token %u of row %d is outside the row (V = %d)", tokens[i], i, V); return DSM_ERR_INVALID; }
+  HIPCHK(hipSetDevice(e->device));
+  std::unique_lock<std::shared_mutex> alone(e->api_mu);  // allocates: never beside a capture
+  float *d_logits = nullptr, *d_lp = nullptr, *d_top_lp = nullptr;
+  uint32_t *d_tok = nullptr, *d_top_id = nullptr;
+  const size_t rows = (size_t)n, top = rows * DSM_SCORES_MAX_TOP;
+  int rc = e->dalloc(&d_logits, rows * (size_t)V, false);
+  if (!rc) rc = e->dalloc(&d_tok, rows, false);
+  if (!rc) rc = e->dalloc(&d_lp, rows, false);
+  if (!rc) rc = e->dalloc(&d_top_id, top, false);
+  if (!rc) rc = e->dalloc(&d_top_lp, top, false);
+  std::vector<uint32_t> h_id(top);
+  std::vector<float> h_lp(top);
+  hipStream_t st = e->s_model;
+  auto run = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(d_logits, logits, sizeof(float) * rows * (size_t)V, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_tok, tokens, sizeof(uint32_t) * rows, hipMemcpyHostToDevice, st));
+    if (int lrc = launch_token_scores(e, st, n, d_logits, V, d_tok, top_n, d_lp, d_top_id, d_top_lp)) return lrc;
+    HIPCHK(hipMemcpyAsync(logprob_out, d_lp, sizeof(float) * rows, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_id.data(), d_top_id, sizeof(uint32_t) * top, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_lp.data(), d_top_lp, sizeof(float) * top, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  };
+  if (!rc) rc = run();
+  for (void* p : {(void*)d_logits, (void*)d_tok, (void*)d_lp, (void*)d_top_id, (void*)d_top_lp}) e->dfree(p);
+  if (rc) return rc;
+  for (size_t i = 0; i < rows && top_n > 0; ++i) {
+    memcpy(top_ids_out + i * (size_t)top_n, &h_id[i * DSM_SCORES_MAX_TOP], sizeof(uint32_t) * (size_t)top_n);
+    memcpy(top_logprobs_out + i * (size_t)top_n, &h_lp[i * DSM_SCORES_MAX_TOP], sizeof(float) * (size_t)top_n);
+  }
+  return 0;
 }
 
 int dsm_asr_reset_slot(dsm_engine* e, int slot) {

@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "dsm_numerics.h"
 #include "dsm_sampling.h"
+#include "dsm_token_scores.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short dsm_bf16x8 __attribute__((ext_vector_type(8)));
@@ -1668,10 +1669,138 @@ __global__ void lm_gumbel_kernel(const float* __restrict__ logits, int V, float 
   }
 }
 
+__device__ __forceinline__ float dsm_unpaired(float v);  // below, with the SEANet front end that first needed it
+
+// Token scores (dsm_token_scores.h; this project's own, off by default): log-probability of the step's text token and the top_n
+// best entries of its logits row.  One 256-thread workgroup per batch row, launched behind lm_argmax_kernel / lm_gumbel_kernel on
+// the same stream, whose text_out it reads.  1 + max(top_n, 1) passes over the row, any V >= 1.  STAGED (rows up to
+// DSM_SCORES_STAGE_MAX floats: 32 KB at V = 8000): the first pass copies the row into dynamic LDS and the others read it there —
+// thread t only ever touches entries j = t (mod 256), its own copies, so the row needs no barrier; a longer row is re-read from
+// L2 in every pass.  Every pick is a block reduction over (value, id) pairs in the order "value descending, id ascending"
+// restricted to the entries behind the previous pick — exact, no float sort; the exp-sum follows the lane / tree order of the
+// header, so the host function gives the same bits.
+// lp [rows], top_id / top_lp [rows][DSM_SCORES_MAX_TOP]: entries top_n .. 7 are written as padding.
+#define DSM_SCORES_STAGE_MAX 15360  // 60 KB of dynamic LDS beside 1 KB static: inside the default 64 KB per workgroup
+struct ScorePick {
+  float v;
+  uint32_t i;
+};
+// first of the order among the block's candidates; the same in every thread after the call.  sv / si: 4 entries of LDS.
+__device__ inline ScorePick block_score_first(float bv, uint32_t bi, float* sv, uint32_t* si) {
+  for (int off = 32; off >= 1; off >>= 1) {  // (a lane beyond the wave's end gets its own pair back: harmless for a maximum)
+    const float ov = __shfl_down(bv, off);
+    const uint32_t oi = (uint32_t)__shfl_down((int)bi, off);
+    if (dsm_score_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sv[threadIdx.x >> 6] = bv;
+    si[threadIdx.x >> 6] = bi;
+  }
+  __syncthreads();
+  bv = sv[0];
+  bi = si[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w)
+    if (dsm_score_before(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
+  __syncthreads();
+  return ScorePick{bv, bi};
+}
+
+template <bool STAGED>
+__global__ void __launch_bounds__(256) lm_token_scores_kernel(const float* __restrict__ logits, int V, const uint32_t* __restrict__ text_out,
+                                                              int top_n, float* __restrict__ lp, uint32_t* __restrict__ top_id,
+                                                              float* __restrict__ top_lp) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* lg = logits + (long)b * V;
+  extern __shared__ __align__(16) float srow[];  // STAGED: V floats
+  __shared__ float sv[4];
+  __shared__ uint32_t si[4];
+  __shared__ float sp[DSM_SCORES_LANES];
+  // A thread walks its entries UN at a time: UN independent loads in flight, then the compares in ascending j.  An entry
+  // beyond the row is a NaN, which no comparison picks.
+  constexpr int UN = 8, STEP = UN * DSM_SCORES_LANES;
+  const float beyond = dsm_u32_as_f32(0x7FC00000u);
+  // round 0: the first entry of the order, whose value is m; the pass that stages the row
+  float bv = -DSM_INF_F;
+  uint32_t bi = DSM_SCORES_NONE;
+  for (int j0 = tid; j0 < V; j0 += STEP) {
+    float v[UN];
+#pragma unroll
+    for (int k = 0; k < UN; ++k) v[k] = j0 + k * DSM_SCORES_LANES < V ? lg[j0 + k * DSM_SCORES_LANES] : beyond;
+#pragma unroll
+    for (int k = 0; k < UN; ++k) {
+      const int j = j0 + k * DSM_SCORES_LANES;
+      if (STAGED && j < V) srow[j] = v[k];
+      if (dsm_score_before(v[k], (uint32_t)j, bv, bi)) { bv = v[k]; bi = (uint32_t)j; }
+    }
+  }
+  ScorePick prev = block_score_first(bv, bi, sv, si);
+  if (prev.i == DSM_SCORES_NONE) prev.v = -DSM_INF_F;  // a row of NaN alone
+  const float m = prev.v;
+  // the picks: round r's stays in thread r's registers (top_n <= 8 < 256)
+  float my_v = prev.v;
+  uint32_t my_i = prev.i;
+  for (int r = 1; r < top_n; ++r) {
+    bv = -DSM_INF_F;
+    bi = DSM_SCORES_NONE;
+    if (prev.i != DSM_SCORES_NONE) {
+      for (int j0 = tid; j0 < V; j0 += STEP) {
+        float v[UN];
+#pragma unroll
+        for (int k = 0; k < UN; ++k) {
+          const int j = j0 + k * DSM_SCORES_LANES;
+          v[k] = j < V ? (STAGED ? srow[j] : lg[j]) : beyond;
+        }
+#pragma unroll
+        for (int k = 0; k < UN; ++k) {
+          const uint32_t j = (uint32_t)(j0 + k * DSM_SCORES_LANES);
+          if (dsm_score_behind(v[k], j, prev.v, prev.i) && dsm_score_before(v[k], j, bv, bi)) { bv = v[k]; bi = j; }
+        }
+      }
+    }
+    prev = block_score_first(bv, bi, sv, si);
+    if (prev.i == DSM_SCORES_NONE) prev.v = -DSM_INF_F;
+    if (tid == r) { my_v = prev.v; my_i = prev.i; }
+  }
+  float p = 0.0f;
+  for (int j0 = tid; j0 < V; j0 += STEP) {  // the lane's terms in ascending j, one f32 add each
+    float v[UN];
+#pragma unroll
+    for (int k = 0; k < UN; ++k) {
+      const int j = j0 + k * DSM_SCORES_LANES;
+      v[k] = j < V ? (STAGED ? srow[j] : lg[j]) : beyond;
+    }
+#pragma unroll
+    for (int k = 0; k < UN; ++k) v[k] = dsm_expf(dsm_unpaired(v[k] - m));
+#pragma unroll
+    for (int k = 0; k < UN; ++k)
+      if (j0 + k * DSM_SCORES_LANES < V) p = dsm_unpaired(p + v[k]);
+  }
+  sp[tid] = p;
+  __syncthreads();
+  if (tid < 128) sp[tid] = sp[tid] + sp[tid + 128];
+  __syncthreads();
+  if (tid < 64) {  // wave 0: lane t of level `off` adds lane t + off, which is the tree of dsm_score_tree_sum for t < off
+    float q = sp[tid] + sp[tid + 64];
+    for (int off = 32; off >= 1; off >>= 1) q = q + __shfl_down(q, off);
+    if (tid == 0) sp[0] = q;
+  }
+  __syncthreads();
+  const float log_s = dsm_logf(sp[0]);
+  if (tid == 0) {
+    const uint32_t tok = text_out[b];
+    lp[b] = tok < (uint32_t)V ? dsm_score_logprob(lg[tok], m, log_s) : dsm_u32_as_f32(0x7FC00000u);
+  }
+  if (tid < DSM_SCORES_MAX_TOP) {
+    const bool have = tid < top_n && my_i != DSM_SCORES_NONE;
+    top_id[(long)b * DSM_SCORES_MAX_TOP + tid] = have ? my_i : DSM_SCORES_NONE;
+    top_lp[(long)b * DSM_SCORES_MAX_TOP + tid] = have ? dsm_score_logprob(my_v, m, log_s) : -DSM_INF_F;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // TTS glue — core/tts_streaming.rs:117-242, core/lm.rs:640-684, :983-995
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float dsm_unpaired(float v);  // below, with the SEANet front end that first needed it
 
 // tokens [B][1+nc] int32: text token, then one entry per codebook; -1 = None ("literal zeros": the embedding is skipped)
 // x, xin ("lm.input": x is overwritten by the layers) and tokens start at the group's first row r0.  cond [slots][d] / cond_on

@@ -113,11 +113,16 @@ struct MpR {
 const char* kInNames[] = {"Init", "Marker", "Audio", "OggOpus", "Ping"};
 const char* kOutNames[] = {"Word", "EndWord", "Marker", "Step", "Error", "Ready"};
 
-void encode_out(std::vector<uint8_t>& buf, const dsm_out_msg& m) {  // field order = declaration order (srv/asr.rs:25-34)
+// word_lp: null, or a Word's { logprob, min_logprob } (dsm_worker_set_word_scores) — two more entries behind the reference's
+// fields; a map, so decoders that do not know the keys skip them
+void encode_out(std::vector<uint8_t>& buf, const dsm_out_msg& m, const double* word_lp = nullptr) {  // field order = declaration order (srv/asr.rs:25-34)
   MpW w{buf};
   auto head = [&](size_t fields) { w.map(1 + fields); w.str("type"); w.str(kOutNames[m.kind]); };
   switch (m.kind) {
-    case DSM_OUT_WORD: head(2); w.str("text"); w.str(m.text ? m.text : ""); w.str("start_time"); w.f64(m.time); break;
+    case DSM_OUT_WORD:
+      head(word_lp ? 4 : 2); w.str("text"); w.str(m.text ? m.text : ""); w.str("start_time"); w.f64(m.time);
+      if (word_lp) { w.str("logprob"); w.f64(word_lp[0]); w.str("min_logprob"); w.f64(word_lp[1]); }
+      break;
     case DSM_OUT_ENDWORD: head(1); w.str("stop_time"); w.f64(m.time); break;
     case DSM_OUT_MARKER: head(1); w.str("id"); w.sint(m.id); break;
     case DSM_OUT_STEP:
@@ -245,6 +250,8 @@ struct dsm_worker {
   std::unique_ptr<dsm_spm> tok;  // dsm_worker_set_tokenizer_file: Word.text when no detok callback is set
   dsm_opus_decode_fn opus = nullptr;
   void* opus_user = nullptr;
+  dsm_engine* eng = nullptr;  // dsm_worker_create: the engine behind `be` (null with a caller-supplied backend)
+  bool word_scores = false;   // dsm_worker_set_word_scores
   std::mutex mu;
   std::string err;
 
@@ -263,12 +270,12 @@ struct dsm_worker {
     }
     return false;
   }
-  void send(int slot, const dsm_out_msg& m, uint64_t ref_channel_id) {  // Channel::send
+  void send(int slot, const dsm_out_msg& m, uint64_t ref_channel_id, const double* word_lp = nullptr) {  // Channel::send
     WChannel& c = ch[slot];
     if (!c.open || c.id != ref_channel_id) return;  // the slot was re-assigned since the step was built
     if (c.out_closed) { c.open = false; return; }   // send error -> *channel = None
     c.out.emplace_back();
-    encode_out(c.out.back(), m);
+    encode_out(c.out.back(), m, word_lp);
   }
 };
 
@@ -384,7 +391,9 @@ int dsm_worker_create(dsm_engine* e, dsm_worker** out) {
   be.encode_async = be_encode_async;
   be.step_ticket = be_step_ticket;
   be.text_out_vocab_size = e->cfg.text_out_vocab_size;
-  return dsm_worker_create_with_backend(&be, out);
+  const int rc = dsm_worker_create_with_backend(&be, out);
+  if (rc == 0) (*out)->eng = e;
+  return rc;
 }
 
 #endif  // DSM_HOST_ONLY
@@ -428,6 +437,18 @@ int dsm_worker_set_tokenizer_file(dsm_worker* w, const char* path) {
     return DSM_ERR_INVALID;
   }
   w->tok.reset(tok);
+  return 0;
+}
+
+int dsm_worker_set_word_scores(dsm_worker* w, int on) {
+  if (!w) return DSM_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (!w->eng) { w->err = "word scores need the engine as backend (dsm_worker_create): a caller-supplied backend has no scores"; return DSM_ERR_STATE; }
+#ifndef DSM_HOST_ONLY
+  if (on && w->eng->scores_top_n < 0)
+    if (int rc = dsm_asr_set_token_scores(w->eng, 0)) { w->err = dsm_last_error(w->eng); return rc; }
+#endif
+  w->word_scores = on != 0;
   return 0;
 }
 
@@ -710,6 +731,18 @@ int dsm_worker_step_model(dsm_worker* w) {
     if (attempt == 1) { w->err = "backend token list changed between two polls"; return DSM_ERR_STATE; }
     toks.assign(need, 0);
   }
+  // Word.logprob / min_logprob: the engine's per-token scores, parallel to toks.  Scores switched off behind the worker's back:
+  // the words go out without the two keys.
+  std::vector<float> lps;
+  bool have_lps = false;
+#ifndef DSM_HOST_ONLY
+  if (w->word_scores && w->eng) {
+    lps.assign(toks.size(), 0.0f);
+    const int got = dsm_asr_poll_word_scores(w->eng, lps.data(), (int)lps.size());
+    have_lps = got >= 0;
+    if (have_lps) lps.resize((size_t)got);
+  }
+#endif
   for (int i = 0; i < n; ++i) {
     const dsm_asr_msg& am = msgs[i];
     dsm_out_msg om{};
@@ -732,7 +765,16 @@ int dsm_worker_step_model(dsm_worker* w) {
         for (int j = 0; j < am.n_tokens; ++j) textbuf += (j ? " " : "") + std::to_string(tk[j]);
       }
       om.kind = DSM_OUT_WORD; om.text = textbuf.c_str(); om.time = am.time;
-      w->send(am.batch_idx, om, ref_ids[am.batch_idx]);
+      double word_lp[2] = {0.0, 0.0};  // mean and minimum of the word's token logprobs; left out when one was not recorded (NaN)
+      bool scored = have_lps && am.n_tokens > 0 && (size_t)am.tokens_offset + (size_t)am.n_tokens <= lps.size();
+      for (int j = 0; scored && j < am.n_tokens; ++j) {
+        const double v = (double)lps[(size_t)am.tokens_offset + (size_t)j];
+        if (v != v) { scored = false; break; }
+        word_lp[0] += v;
+        word_lp[1] = j == 0 || v < word_lp[1] ? v : word_lp[1];
+      }
+      if (scored) word_lp[0] /= (double)am.n_tokens;
+      w->send(am.batch_idx, om, ref_ids[am.batch_idx], scored ? word_lp : nullptr);
     } else if (am.kind == DSM_MSG_END_WORD) {
       om.kind = DSM_OUT_ENDWORD; om.time = am.time;
       w->send(am.batch_idx, om, ref_ids[am.batch_idx]);

@@ -241,6 +241,41 @@ int dsm_asr_step_tokens_ticket(dsm_engine*, int ticket, const uint8_t* mask, uin
  * poll again with a larger buffer (dsm_worker_step does exactly that). */
 int dsm_asr_poll_msgs(dsm_engine*, dsm_asr_msg* msgs, int cap, uint32_t* tokens_out, int tokens_cap);
 
+/* ---- token scores: how sure the model was (this project's own; the reference keeps the argmax and drops the logits row,
+ * core/asr.rs:208-215).  Off by default: a step then enqueues exactly what it enqueues without this section.
+ * Definition (csrc/dsm_token_scores.h, bit-identical on host and device): over the raw text logits of a slot, at softmax
+ * temperature 1 — also when cfg.temperature > 0 drew the token with Gumbel noise, where top_ids[0] may differ from the token —
+ *   logprob     log softmax of the step's text token,
+ *   top_n best  the first top_n entries of the row by value descending, then id ascending: id and logprob each; entries beyond
+ *               the vocabulary are id 0xFFFFFFFF, logprob -inf.
+ * Rows of inactive slots are unspecified, like their text token.
+ *   dsm_asr_set_token_scores  top_n = -1 turns scores off, 0 .. DSM_SCORES_MAX_TOP on with that many alternatives;
+ *     DSM_ERR_INVALID otherwise.  Any time between steps; waits for calls in progress on other threads.  A change of the setting
+ *     makes the LM step's graphs settle again (two eager steps), it is not a per-step switch.
+ *   dsm_asr_token_scores      the scores of the last dsm_asr_step_tokens / _step_pcm / _step_tokens_ticket (which bring them to the
+ *     host with the tokens): logprob_out [B], top_ids_out / top_logprobs_out [B][top_n] or NULL.  Returns top_n.  DSM_ERR_STATE
+ *     while scores are off, or before the first such step since the setting changed.
+ *   dsm_asr_token_scores_dev  for the *_dev callers: the engine's device buffers, valid after dsm_sync and overwritten by the next
+ *     step; logprob [B], the two top buffers [B][DSM_SCORES_MAX_TOP] (row stride DSM_SCORES_MAX_TOP whatever top_n).  Returns top_n.
+ *   dsm_asr_poll_word_scores  parallel to the tokens_out of dsm_asr_poll_msgs: entry msg.tokens_offset + i is the logprob of that
+ *     Word's token i; NaN = not recorded (the token came while scores were off, or with an imported snapshot).  Returns the
+ *     number of floats written (<= cap).  DSM_ERR_STATE while scores are off.
+ *   dsm_token_scores_host     host only, no device needed (like dsm_slot_blob_info): the definition computed serially for one
+ *     row of V logits and a token.  DSM_ERR_INVALID for V < 1, token >= V, top_n outside 0 .. DSM_SCORES_MAX_TOP, or a NULL
+ *     pointer that is needed (top_ids / top_logprobs may be NULL when top_n is 0).
+ *   dsm_debug_token_scores    test aid: runs the step's KERNEL on caller-supplied rows — host logits [n][V] and tokens [n] in,
+ *     host logprob_out [n], top_ids_out / top_logprobs_out [n][top_n] out.  Synchronises the model stream. */
+#define DSM_SCORES_MAX_TOP 8
+int dsm_asr_set_token_scores(dsm_engine*, int top_n);
+int dsm_asr_token_scores(dsm_engine*, float* logprob_out /*[B]*/, uint32_t* top_ids_out /*[B][top_n] or NULL*/,
+                         float* top_logprobs_out /*[B][top_n] or NULL*/);
+int dsm_asr_token_scores_dev(dsm_engine*, const float** d_logprob, const uint32_t** d_top_ids, const float** d_top_logprobs);
+int dsm_asr_poll_word_scores(dsm_engine*, float* logprobs_out, int cap);
+int dsm_token_scores_host(const float* logits, int V, uint32_t token, int top_n, float* logprob, uint32_t* top_ids,
+                          float* top_logprobs);
+int dsm_debug_token_scores(dsm_engine*, const float* logits, int n, int V, const uint32_t* tokens, int top_n,
+                           float* logprob_out, uint32_t* top_ids_out, float* top_logprobs_out);
+
 /* asr::State::reset_batch_idx(slot) — core/asr.rs:257-266, srv/batched_asr.rs:467-471.
  * Resets the LM slot (KV index/position, item state) and the MODEL side's Mimi slot.
  * The reference never resets the ENCODER thread's Mimi clone;
@@ -261,6 +296,9 @@ int dsm_asr_set_seed(dsm_engine*, int slot, uint64_t seed);
  *   host     the word-assembly item (step index, pending word tokens, unended_word, last stop time).
  * NOT in a snapshot: the Mimi DECODE state (dsm_mimi_decode_step), the activation scratch and anything else a step overwrites
  * before it reads, the worker's channels (dsm_worker), captured graphs, metrics, and the TTS engine (whose blob format, not yet its calls, is dsm_tts_slot_blob_info below).
+ * Nor the token scores (dsm_asr_set_token_scores): neither the setting nor the scores of a pending word's tokens — after an import
+ * or a move those read NaN in dsm_asr_poll_word_scores, tokens that arrive later carry real scores, and the blob's bytes do not
+ * depend on whether the exporter had scores on.
  * After an import the stream continues bit for bit — codes, tokens, VAD, words — as if it had stayed where it was.  One
  * exception, stated: a slot exported from a Mimi side that has never stepped and imported into a side that has behaves like a
  * reset slot there (zero left pad) — the module-level first call that would have replicated its first frame cannot be moved.
@@ -813,6 +851,12 @@ void dsm_worker_set_detokenizer(dsm_worker*, dsm_detok_fn, void* user);
  * dsm_spm_load; DSM_ERR_INVALID also when the model has more pieces than the backend's text_out_vocab_size (an engine-backed
  * worker knows its own).  The previous tokenizer, if any, stays on failure. */
 int dsm_worker_set_tokenizer_file(dsm_worker*, const char* path);
+/* on != 0: every Word message becomes a map of type, text, start_time, logprob and min_logprob — the mean and the minimum (f64)
+ * of the word's token log-probabilities (dsm_asr_poll_word_scores); both keys are left out of a Word one of whose tokens has no
+ * recorded score.  Turns the engine's token scores on (top_n 0) if they are off.  Off, the default, keeps the reference's wire
+ * bytes; decoders that ignore unknown map keys (serde's default, dsm_outmsg_decode) read either form.  DSM_ERR_STATE on a worker
+ * with a caller-supplied backend (dsm_worker_create_with_backend), which has no scores. */
+int dsm_worker_set_word_scores(dsm_worker*, int on);
 /* BatchedAsr::channels (:796-808) + the Init that handle_socket / handle_query send (:833,893).  Returns the slot
  * (batch_idx) or DSM_ERR_STATE when no slot is free ("Server at capacity - no free channels available", :875). */
 int dsm_worker_open(dsm_worker*, uint64_t* channel_id);
