@@ -160,7 +160,24 @@ ABI_SYMBOLS = [
     "dsm_tts_slot_blob_info",
     "dsm_asr_set_token_scores", "dsm_asr_token_scores", "dsm_asr_token_scores_dev", "dsm_asr_poll_word_scores",
     "dsm_token_scores_host", "dsm_debug_token_scores", "dsm_worker_set_word_scores",
+    "dsm_asr_set_text_bias", "dsm_asr_bias_create", "dsm_asr_bias_create_text", "dsm_asr_bias_destroy", "dsm_asr_bias_info",
+    "dsm_asr_set_bias", "dsm_asr_bias_state", "dsm_text_bias_compile", "dsm_text_bias_pick_host", "dsm_debug_text_pick",
+    "dsm_worker_set_bias",
 ]
+BIAS_MAX_TOKENS, BIAS_MAX_KEYWORD_TOKENS, BIAS_MAX_NODES, BIAS_MAX_SETS = 1024, 32, 65535, 256  # DSM_BIAS_MAX_*
+BIAS_DEAD = 0xFFFFFFFF  # DSM_BIAS_DEAD: the trie node of a slot inside a word that left the trie
+
+
+class BiasToken(C.Structure):
+    """dsm_bias_token (include/dsm.h)."""
+    _fields_ = [("token", C.c_uint32), ("bias", C.c_float)]
+
+
+class BiasKeyword(C.Structure):
+    """dsm_bias_keyword (include/dsm.h): one word as its piece ids, and its boost in logit units."""
+    _fields_ = [("tokens", C.POINTER(C.c_uint32)), ("n_tokens", C.c_int), ("boost", C.c_float)]
+
+
 SCORES_MAX_TOP = 8  # DSM_SCORES_MAX_TOP
 SCORES_NONE = 0xFFFFFFFF  # the id of a top-N entry beyond the vocabulary
 TTS_COND_LUT, TTS_COND_CONTINUOUS = 0, 1  # DSM_TTS_COND_*
@@ -381,6 +398,23 @@ def load_library(path=None):
     for name in ("dsm_asr_set_token_scores", "dsm_asr_token_scores", "dsm_asr_token_scores_dev", "dsm_asr_poll_word_scores",
                  "dsm_token_scores_host", "dsm_debug_token_scores", "dsm_worker_set_word_scores"):
         getattr(lib, name).restype = C.c_int
+    lib.dsm_asr_set_text_bias.argtypes = [vp, C.c_int]
+    lib.dsm_asr_bias_create.argtypes = [vp, C.POINTER(BiasToken), C.c_int, C.POINTER(BiasKeyword), C.c_int, C.POINTER(C.c_int)]
+    lib.dsm_asr_bias_create_text.argtypes = [vp, vp, C.POINTER(C.c_char_p), fp, C.c_int, C.POINTER(BiasToken), C.c_int, C.POINTER(C.c_int)]
+    lib.dsm_asr_bias_destroy.argtypes = [vp, C.c_int]
+    lib.dsm_asr_bias_info.argtypes = [vp, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_size_t)]
+    lib.dsm_asr_set_bias.argtypes = [vp, C.c_int, C.c_int]
+    lib.dsm_asr_bias_state.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
+    lib.dsm_text_bias_compile.argtypes = [C.POINTER(BiasToken), C.c_int, C.POINTER(BiasKeyword), C.c_int, C.c_int, u32p, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]
+    lib.dsm_text_bias_pick_host.argtypes = [u32p, C.c_size_t, C.c_uint32, fp, C.c_int, C.c_float, u32p, C.c_uint64,
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.dsm_debug_text_pick.argtypes = [vp, C.c_int, fp, C.c_int, C.c_int, u32p, C.c_float, u32p, vp, u32p, u32p]
+    lib.dsm_worker_set_bias.argtypes = [vp, C.c_int, C.c_int]
+    for name in ("dsm_asr_set_text_bias", "dsm_asr_bias_create", "dsm_asr_bias_create_text", "dsm_asr_bias_destroy", "dsm_asr_bias_info",
+                 "dsm_asr_set_bias", "dsm_asr_bias_state", "dsm_text_bias_compile", "dsm_text_bias_pick_host", "dsm_debug_text_pick",
+                 "dsm_worker_set_bias"):
+        getattr(lib, name).restype = C.c_int
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
         getattr(lib, name).restype = C.c_int
@@ -519,6 +553,58 @@ def token_scores_host(logits, token, top_n=0):
         e.code = rc
         raise e
     return lp[0], ids, lps
+
+
+def _bias_args(tokens, keywords):
+    """((token, bias), ...), ((piece ids, boost), ...) -> the two C arrays with their counts, and what must stay alive."""
+    tokens, keywords = list(tokens or ()), list(keywords or ())
+    for t, _ in tokens:
+        if not 0 <= int(t) < 2 ** 32:
+            raise DsmError("text bias: token outside uint32")
+    tk = (BiasToken * max(len(tokens), 1))(*[BiasToken(int(t), float(v)) for t, v in tokens])
+    keep, kws = [], (BiasKeyword * max(len(keywords), 1))()
+    for i, (ids, boost) in enumerate(keywords):
+        a = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        keep.append(a)
+        kws[i] = BiasKeyword(a.ctypes.data_as(C.POINTER(C.c_uint32)) if a.size else None, a.size, float(boost))
+    return tk, len(tokens), kws, len(keywords), keep
+
+
+def _bias_fail(call, rc):
+    e = DsmError(f"{call}: error {rc}: {load_library().dsm_last_error(None).decode(errors='replace')}")
+    e.code = rc
+    return e
+
+
+def text_bias_compile(tokens, keywords, V):
+    """dsm_text_bias_compile: the flat table (uint32 array, csrc/dsm_text_bias.h) of a bias set.  tokens: (token, bias) pairs,
+    bias finite or -inf; keywords: (piece ids, boost) pairs, each ONE word.  Host only, no device needed."""
+    lib = load_library()
+    tk, nt, kws, nk, _keep = _bias_args(tokens, keywords)
+    need = C.c_size_t(0)
+    rc = lib.dsm_text_bias_compile(tk, nt, kws, nk, int(V), None, 0, C.byref(need))
+    if rc < 0:
+        raise _bias_fail("dsm_text_bias_compile", rc)
+    out = np.zeros(need.value, dtype=np.uint32)
+    rc = lib.dsm_text_bias_compile(tk, nt, kws, nk, int(V), _ptr(out), out.size, None)
+    if rc < 0:
+        raise _bias_fail("dsm_text_bias_compile", rc)
+    return out
+
+
+def text_bias_pick_host(table, node, logits, temperature=0.0, rng_key=None, rng_pos=0):
+    """dsm_text_bias_pick_host: (token, next node) of one row of f32 logits by the definition of csrc/dsm_text_bias.h, computed
+    serially on the host.  table: a compiled table, or None for "no set" (the node comes back unchanged)."""
+    lib = load_library()
+    row = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    t = None if table is None else np.ascontiguousarray(table, dtype=np.uint32).reshape(-1)
+    key = None if rng_key is None else np.ascontiguousarray(rng_key, dtype=np.uint32).reshape(8)
+    tok, nxt = C.c_uint32(0), C.c_uint32(0)
+    rc = lib.dsm_text_bias_pick_host(_ptr(t), 0 if t is None else t.size, int(node), _ptr(row), row.size, float(temperature),
+                                     _ptr(key), int(rng_pos), C.byref(tok), C.byref(nxt))
+    if rc < 0:
+        raise _bias_fail("dsm_text_bias_pick_host", rc)
+    return tok.value, nxt.value
 
 
 def _ptr(a):
@@ -708,6 +794,15 @@ class Worker:
         """dsm_worker_set_word_scores: Word messages carry logprob / min_logprob (mean and minimum of the word's token
         log-probabilities).  Engine-backed workers only."""
         rc = self.lib.dsm_worker_set_word_scores(self.h, 1 if on else 0)
+        if rc < 0:
+            e = DsmError(f"dsm error {rc}: {self._err()}")
+            e.code = rc
+            raise e
+
+    def set_bias(self, slot, handle):
+        """dsm_worker_set_bias: attach an open channel's slot to a bias set of the engine (0 detaches); the worker detaches it
+        when the channel closes.  Engine-backed workers only."""
+        rc = self.lib.dsm_worker_set_bias(self.h, int(slot), int(handle or 0))
         if rc < 0:
             e = DsmError(f"dsm error {rc}: {self._err()}")
             e.code = rc
@@ -1052,6 +1147,65 @@ class AsrEngine:
         self._check(self.lib.dsm_debug_token_scores(self.h, _ptr(logits), n, V, _ptr(tokens), k, _ptr(lp),
                                                     _ptr(ids) if k > 0 else None, _ptr(lps) if k > 0 else None))
         return lp, ids, lps
+
+    # text bias (include/dsm.h "text bias")
+    def set_text_bias(self, on):
+        """Engine-wide switch, off by default: on, every slot's text token is picked by lm_pick_biased_kernel over the raw
+        logits plus the biases of the set the slot is attached to."""
+        self._check(self.lib.dsm_asr_set_text_bias(self.h, 1 if on else 0))
+
+    def bias_create(self, tokens=(), keywords=()):
+        """tokens: (token, bias) pairs, bias finite or -inf (a ban); keywords: (piece ids, boost) pairs, each ONE word.
+        Returns the set's handle (positive, never reused)."""
+        tk, nt, kws, nk, _keep = _bias_args(tokens, keywords)
+        h = C.c_int(0)
+        self._check(self.lib.dsm_asr_bias_create(self.h, tk, nt, kws, nk, C.byref(h)))
+        return h.value
+
+    def bias_create_text(self, tokenizer, words, boosts, tokens=()):
+        """The keywords as text: each word is encoded alone with `tokenizer` (a Tokenizer)."""
+        words = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in words]
+        arr = (C.c_char_p * max(len(words), 1))(*words)
+        b = np.ascontiguousarray(boosts, dtype=np.float32).reshape(-1)
+        if b.size != len(words):
+            raise DsmError("bias_create_text: one boost per word")
+        tk, nt, _, _, _keep = _bias_args(tokens, ())
+        h = C.c_int(0)
+        self._check(self.lib.dsm_asr_bias_create_text(self.h, tokenizer.h, arr, _ptr(b), len(words), tk, nt, C.byref(h)))
+        return h.value
+
+    def bias_destroy(self, handle):
+        self._check(self.lib.dsm_asr_bias_destroy(self.h, int(handle)))
+
+    def bias_info(self, handle):
+        """dict(nodes, edges, tokens, refs, device_bytes) of a set."""
+        v = [C.c_int(0) for _ in range(4)]
+        nbytes = C.c_size_t(0)
+        self._check(self.lib.dsm_asr_bias_info(self.h, int(handle), *[C.byref(x) for x in v], C.byref(nbytes)))
+        return dict(nodes=v[0].value, edges=v[1].value, tokens=v[2].value, refs=v[3].value, device_bytes=nbytes.value)
+
+    def set_bias(self, slot, handle):
+        """Attach `slot` to a set; 0 (or None) detaches."""
+        self._check(self.lib.dsm_asr_set_bias(self.h, int(slot), int(handle or 0)))
+
+    def bias_state(self, slot):
+        """(set handle or 0, trie node) of the slot as of the last finished step."""
+        s, n = C.c_int(0), C.c_uint32(0)
+        self._check(self.lib.dsm_asr_bias_state(self.h, int(slot), C.byref(s), C.byref(n)))
+        return s.value, n.value
+
+    def debug_text_pick(self, handle, logits, nodes, temperature=0.0, rng_keys=None, rng_pos=None):
+        """Test aid: the step's pick KERNEL on caller-supplied rows.  logits [n, V] f32, nodes [n]; for temperature > 0 rng_keys
+        [n, 8] u32 and rng_pos [n] u64 -> (tokens [n] u32, next nodes [n] u32)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        n, V = logits.shape
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(n)
+        keys = None if rng_keys is None else np.ascontiguousarray(rng_keys, dtype=np.uint32).reshape(n, 8)
+        pos = None if rng_pos is None else np.ascontiguousarray(rng_pos, dtype=np.uint64).reshape(n)
+        toks, nxt = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._check(self.lib.dsm_debug_text_pick(self.h, int(handle or 0), _ptr(logits), n, V, _ptr(nodes), float(temperature),
+                                                 _ptr(keys), _ptr(pos), _ptr(toks), _ptr(nxt)))
+        return toks, nxt
 
     def reset_batch_idx(self, slot):
         self._check(self.lib.dsm_asr_reset_slot(self.h, slot))

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <map>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -296,6 +297,23 @@ struct dsm_engine : DsmDevice {
   float *scores_lp = nullptr, *scores_top_lp = nullptr, *h_scores_lp = nullptr, *h_scores_top_lp = nullptr;
   uint32_t *scores_top_id = nullptr, *h_scores_top_id = nullptr;
   size_t scores_host_steps = 0;
+  // text bias (dsm_asr_set_text_bias; dsm_text_bias.h): the switch, and what lm_pick_biased_kernel reads — the descriptor table
+  // [DSM_BIAS_MAX_SETS] (entry 0 = no set), each slot's descriptor index [B] and trie node [B] — allocated by the first call of
+  // the section.  Host side: the sets by handle (positive, never reused), each with its table's host copy and its reference
+  // count, and the handle each slot is attached to.
+  struct BiasSet {
+    int index = 0;  // its entry of bias_sets_d
+    std::vector<uint32_t> words;
+    uint32_t* d_table = nullptr;
+    int refs = 0;
+  };
+  bool bias_on = false;
+  BiasSetDesc* bias_sets_d = nullptr;
+  uint32_t *bias_slot_set = nullptr, *bias_slot_node = nullptr;
+  std::map<int, BiasSet> bias_sets;
+  std::vector<int> bias_slot_handle;  // [B], 0 = none
+  int bias_next_handle = 1;
+  std::mutex bias_mu;  // the host side of the section (the worker's threads both reach it)
   dsm_metrics metrics{};
   // run-ahead pipeline between the encoder thread and the model thread (dsm_mimi_encode_step_async /
   // dsm_asr_step_tokens_ticket): the reference's sync_channel(100) of PipelineMsg (srv/batched_asr.rs:291), here a ring of
@@ -1124,6 +1142,7 @@ int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, 
 
 #include "dsm_engine_api.inc"
 #include "dsm_slot_state.inc"
+#include "dsm_text_bias.inc"
 #include "dsm_tts.inc"
 #include "dsm_tts_voice.inc"
 #include "dsm_tts_slot_state.inc"

@@ -463,6 +463,30 @@ int launch_token_scores(DsmDevice* e, hipStream_t st, int rows, const float* log
   return 0;
 }
 
+// Text bias: slot's trie node = `node`, on `st`.  Nothing to do until the section's buffers exist (a slot attached later
+// takes its node from dsm_asr_set_bias).
+int bias_put_node(dsm_engine* e, hipStream_t st, int slot, uint32_t node) {
+  if (!e->bias_slot_node) return 0;
+  hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, st, e->bias_slot_node + slot, node, 1L);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// lm_pick_biased_kernel over `rows` rows of V <= DSM_SCORES_STAGE_MAX logits (the callers check), staged in dynamic LDS
+int launch_pick_biased(DsmDevice* e, hipStream_t st, int rows, const float* logits, int V, float temperature, const uint32_t* rng_key,
+                       unsigned long long* rng_pos, const BiasSetDesc* sets, const uint32_t* slot_set, uint32_t* slot_node,
+                       uint32_t* text_out, uint32_t* text_token, uint8_t* first_step, const uint8_t* active) {
+  const size_t lds = sizeof(float) * (size_t)V;
+  if (temperature > 0.0f)
+    hipLaunchKernelGGL(lm_pick_biased_kernel<true>, dim3(rows), dim3(256), lds, st, logits, V, temperature, rng_key, rng_pos, sets, slot_set,
+                       slot_node, text_out, text_token, first_step, active);
+  else
+    hipLaunchKernelGGL(lm_pick_biased_kernel<false>, dim3(rows), dim3(256), lds, st, logits, V, temperature, rng_key, rng_pos, sets, slot_set,
+                       slot_node, text_out, text_token, first_step, active);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // asr::State::step_tokens device part — core/asr.rs:165-217, for the slots [b0, b0+nb) of one stream group.
 // Part 1 (eager, three launches): the group's private mask copy, token shift + pad select + embedding sum, next_codebooks
 // update; it ends with the event that tells the model stream the step's shared inputs (codes, mask) are consumed.
@@ -489,7 +513,12 @@ int lm_group_body(dsm_engine* e, hipStream_t st, int g, uint32_t* d_text_out, fl
     a.Y = logits; a.ymap = plain_map(nb, c.text_out_vocab_size);
     if ((rc = gemm_store<uint16_t>(e, st, a))) return rc;
   }
-  if (c.temperature > 0.0f)
+  if (e->bias_on) {  // dsm_asr_set_text_bias: one launch in place of the two below
+    if ((rc = launch_pick_biased(e, st, nb, logits, c.text_out_vocab_size, c.temperature, s.rng_key + (size_t)b0 * 8, s.rng_pos + b0,
+                                 e->bias_sets_d, e->bias_slot_set + b0, e->bias_slot_node + b0, d_text_out + b0, s.text_token + b0,
+                                 s.first_step + b0, gmask)))
+      return rc;
+  } else if (c.temperature > 0.0f)
     hipLaunchKernelGGL(lm_gumbel_kernel, dim3(nb), dim3(256), 0, st, logits, c.text_out_vocab_size, c.temperature,
                        s.rng_key + (size_t)b0 * 8, s.rng_pos + b0, d_text_out + b0, s.text_token + b0, s.first_step + b0, gmask);
   else
@@ -539,10 +568,12 @@ int lm_group_head(dsm_engine* e, hipStream_t st, int g, const uint32_t* d_codes,
 
 // Rest of the group's step: one hipGraph once settled.  Capture key: the stream's workspace slot, the caller's output
 // pointers (everything else is engine-owned), whether the head already ran the transformer's prefix, and the token-scores
-// setting (off adds nothing to the key; each top_n is a body of its own, since it is a launch argument).
+// setting (off adds nothing to the key; each top_n is a body of its own, since it is a launch argument), and the text-bias
+// switch (off adds nothing either; on is another pick kernel).
 int lm_group_rest(dsm_engine* e, hipStream_t st, int g, uint32_t* d_text_out, float* d_prs_out, bool after_prefix) {
   const uint64_t key = (uint64_t)e->sid(st) ^ ((uint64_t)(uintptr_t)d_text_out << 3) ^ ((uint64_t)(uintptr_t)d_prs_out * 0x9E3779B97F4A7C15ull) ^
-                       (after_prefix ? 0x8000000000000000ull : 0ull) ^ ((uint64_t)(e->scores_top_n + 1) * 0xD6E8FEB86659FD93ull);
+                       (after_prefix ? 0x8000000000000000ull : 0ull) ^ ((uint64_t)(e->scores_top_n + 1) * 0xD6E8FEB86659FD93ull) ^
+                       (e->bias_on ? 0xA24BAED4963EE407ull : 0ull);
   return run_captured(e, *e->g_grp[g], st, key, [&] { return lm_group_body(e, st, g, d_text_out, d_prs_out, after_prefix ? 2 : 0); });
 }
 
@@ -1428,6 +1459,7 @@ int dsm_asr_reset_slot(dsm_engine* e, int slot) {
   hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, st, e->lm.text_token + slot,
                      (uint32_t)e->cfg.text_in_vocab_size - 1, 1L);
   HIPCHK(hipGetLastError());
+  if (int rc = bias_put_node(e, st, slot, 0u)) return rc;  // text bias: the attachment stays, the trie node returns to the root
   return reset_mimi_slot(e, 1, st, slot);
 }
 

@@ -17,6 +17,7 @@
 #include "dsm_numerics.h"
 #include "dsm_sampling.h"
 #include "dsm_token_scores.h"
+#include "dsm_text_bias.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short dsm_bf16x8 __attribute__((ext_vector_type(8)));
@@ -1795,6 +1796,130 @@ __global__ void __launch_bounds__(256) lm_token_scores_kernel(const float* __res
     const bool have = tid < top_n && my_i != DSM_SCORES_NONE;
     top_id[(long)b * DSM_SCORES_MAX_TOP + tid] = have ? my_i : DSM_SCORES_NONE;
     top_lp[(long)b * DSM_SCORES_MAX_TOP + tid] = have ? dsm_score_logprob(my_v, m, log_s) : -DSM_INF_F;
+  }
+}
+
+// Text bias (dsm_text_bias.h; this project's own, off by default): the pick of the step's text token over x = raw logits + the
+// slot's token biases + the boosts of its trie node's edges, and the node's advance.  Stands in for lm_argmax_kernel /
+// lm_gumbel_kernel when dsm_asr_set_text_bias is on: one 256-thread workgroup per batch row of the stream group, one launch, none
+// added.  The row is staged in dynamic LDS (V <= DSM_SCORES_STAGE_MAX, which the switch checks), the two lists are scatter-added
+// there — their entries are distinct, so no atomics; a barrier between them fixes the order of the two adds on a token that is in
+// both — and the pick reads LDS: the raw logits in global memory stay as the GEMM wrote them.  The lists are reached through
+// engine-owned memory only — `sets` (DSM_BIAS_MAX_SETS descriptors; entry 0 is "no set"), the slot's set index and node — so
+// every launch argument is an engine buffer and the step replays as one hipGraph.  The maximum is exact and first-occurrence,
+// so the reduction tree's shape cannot show in the result; it is block_argmax_first's.
+struct BiasSetDesc {
+  const uint32_t* table;  // the set's flat table (dsm_text_bias.h), device memory; null in entry 0 and in free entries
+  uint32_t n_tokens, n_nodes, n_edges, reserved;
+};
+
+template <bool GUMBEL>
+__global__ void __launch_bounds__(256) lm_pick_biased_kernel(const float* __restrict__ logits, int V, float temperature,
+                                                             const uint32_t* __restrict__ rng_key, unsigned long long* __restrict__ rng_pos,
+                                                             const BiasSetDesc* __restrict__ sets, const uint32_t* __restrict__ slot_set,
+                                                             uint32_t* __restrict__ slot_node, uint32_t* __restrict__ text_out,
+                                                             uint32_t* __restrict__ text_token, uint8_t* __restrict__ first_step,
+                                                             const uint8_t* __restrict__ active) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* lg = logits + (long)b * V;
+  extern __shared__ __align__(16) float xrow[];  // V floats
+  __shared__ float sv[256];
+  __shared__ int si[256];
+  __shared__ uint32_t s_child;
+  const uint32_t set = slot_set[b];
+  const bool has_set = set != 0 && set < DSM_BIAS_MAX_SETS;
+  BiasSetDesc d{nullptr, 0u, 0u, 0u, 0u};
+  if (has_set) d = sets[set];
+  const uint32_t node = has_set && d.table ? slot_node[b] : DSM_BIAS_DEAD;
+  const bool live = node < d.n_nodes;  // DEAD (0xFFFFFFFF) is never below a node count
+  // 1: stage the row; thread t owns entries j = t (mod 256), UN independent loads in flight
+  constexpr int UN = 8, STEP = UN * 256;
+  for (int j0 = tid; j0 < V; j0 += STEP) {
+    float v[UN];
+#pragma unroll
+    for (int k = 0; k < UN; ++k) v[k] = j0 + k * 256 < V ? lg[j0 + k * 256] : 0.0f;
+#pragma unroll
+    for (int k = 0; k < UN; ++k)
+      if (j0 + k * 256 < V) xrow[j0 + k * 256] = v[k];
+  }
+  if (tid == 0) s_child = DSM_BIAS_DEAD;
+  __syncthreads();
+  // 2: token biases (a list longer than the block is walked in strides)
+  if (d.table) {
+    const uint32_t* tb = dsm_bias_tokens_of(d.table);
+    for (uint32_t i = tid; i < d.n_tokens; i += 256) {
+      const uint32_t t = tb[2u * i];
+      if (t < (uint32_t)V) xrow[t] = dsm_unpaired(xrow[t] + dsm_u32_as_f32(tb[2u * i + 1u]));
+    }
+  }
+  __syncthreads();
+  // 3: the node's edges, behind the barrier: (l + bias) + boost
+  const uint32_t* edges = nullptr;
+  uint32_t eb = 0, ee = 0;
+  if (live) {
+    const uint32_t* first = dsm_bias_first_of(d.table, d.n_tokens);
+    edges = dsm_bias_edges_of(d.table, d.n_tokens, d.n_nodes);
+    eb = first[node];
+    ee = first[node + 1];
+    if (ee > d.n_edges) ee = d.n_edges;
+    for (uint32_t e = eb + tid; e < ee; e += 256) {
+      const uint32_t t = edges[3u * e];
+      if (t < (uint32_t)V) xrow[t] = dsm_unpaired(xrow[t] + dsm_u32_as_f32(edges[3u * e + 1u]));
+    }
+  }
+  __syncthreads();
+  // 4: the pick over the LDS row
+  float bv = -DSM_INF_F;
+  int bi = 0x7FFFFFFF;
+  unsigned long long pos = 0;
+  const int nblk = (V + 15) >> 4;
+  if (GUMBEL) {
+    uint32_t key[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) key[i] = rng_key[b * 8 + i];
+    pos = rng_pos[b];
+    for (int blk = tid; blk < nblk; blk += 256) {
+      uint32_t w[16];
+      dsm_chacha_block(key, (pos >> 4) + (unsigned long long)blk, 12, w);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int j = 16 * blk + i;
+        if (j < V) {
+          const float v = dsm_gumbel_value(xrow[j], w[i], temperature);
+          if (v > bv || (v == bv && j < bi)) { bv = v; bi = j; }
+        }
+      }
+    }
+  } else {
+    for (int j = tid; j < V; j += 256) {
+      const float v = xrow[j];
+      if (v > bv || (v == bv && j < bi)) { bv = v; bi = j; }
+    }
+  }
+  sv[tid] = bv;
+  si[tid] = bi;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if (tid < off) {
+      const float ov = sv[tid + off];
+      const int oi = si[tid + off];
+      if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
+    }
+    __syncthreads();
+  }
+  const uint32_t tok = si[0] == 0x7FFFFFFF ? 0u : (uint32_t)si[0];
+  // 5: the picked token among the node's edges — tokens are distinct inside a node, so at most one thread finds it
+  for (uint32_t e = eb + tid; e < ee; e += 256)
+    if (edges[3u * e] == tok) s_child = edges[3u * e + 2u];
+  __syncthreads();
+  if (tid == 0) {
+    text_out[b] = tok;
+    if (active[b]) {
+      text_token[b] = tok;
+      first_step[b] = 0;
+      if (GUMBEL) rng_pos[b] = pos + 16ull * (unsigned long long)nblk;
+      if (has_set && d.table) slot_node[b] = dsm_bias_advance(node, tok, live ? s_child : DSM_BIAS_DEAD);
+    }
   }
 }
 

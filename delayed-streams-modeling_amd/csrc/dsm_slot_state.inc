@@ -137,6 +137,8 @@ int slot_apply_items(dsm_engine* e, hipStream_t st, const int* slots, int n, boo
     it.unended_word = in.unended_word != 0;
     it.word_tokens = in.word_tokens;
     it.word_logprobs.assign(in.word_tokens.size(), dsm_u32_as_f32(0x7FC00000u));  // a snapshot carries no scores: not recorded
+    // text bias: the slot keeps its own attachment; where the imported stream stands inside a word is not known
+    if (int rc = bias_put_node(e, st, slots[i], in.step_idx == 0 ? 0u : DSM_BIAS_DEAD)) return rc;
     for (int side = 0; side < (has1 ? 2 : 1); ++side) {
       MimiState& s = e->mimi[side];
       if (s.first_call && s.keep) s.keep_h[(size_t)slots[i]] = (in.side_flags & (DSM_SLOT_SIDE_PRISTINE0 << side)) ? 0 : 1;

@@ -229,6 +229,7 @@ struct WChannel {  // srv/batched_asr.rs:69-116
   std::deque<std::vector<uint8_t>> out;  // out_rx (already serialised: send_loop's job)
   std::deque<float> data;
   size_t steps = 0;
+  int bias_set = 0;  // dsm_worker_set_bias: what the channel's slot is attached to; detached when the channel closes
 };
 
 }  // namespace
@@ -415,7 +416,15 @@ int dsm_worker_create_with_backend(const dsm_worker_backend* be, dsm_worker** ou
   return 0;
 }
 
-void dsm_worker_destroy(dsm_worker* w) { delete w; }
+void dsm_worker_destroy(dsm_worker* w) {
+  if (!w) return;
+#ifndef DSM_HOST_ONLY
+  // dsm_worker_set_bias: what the worker attached it detaches, so that the engine's owner can destroy the sets
+  for (int b = 0; b < w->B && w->eng; ++b)
+    if (w->ch[(size_t)b].bias_set) (void)dsm_asr_set_bias(w->eng, b, 0);
+#endif
+  delete w;
+}
 const char* dsm_worker_last_error(const dsm_worker* w) { return w ? w->err.c_str() : ""; }
 void dsm_worker_set_detokenizer(dsm_worker* w, dsm_detok_fn fn, void* user) {
   if (!w) return;
@@ -449,6 +458,19 @@ int dsm_worker_set_word_scores(dsm_worker* w, int on) {
     if (int rc = dsm_asr_set_token_scores(w->eng, 0)) { w->err = dsm_last_error(w->eng); return rc; }
 #endif
   w->word_scores = on != 0;
+  return 0;
+}
+
+int dsm_worker_set_bias(dsm_worker* w, int slot, int set) {
+  if (!w || slot < 0 || slot >= w->B) return DSM_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (!w->eng) { w->err = "text bias needs the engine as backend (dsm_worker_create): a caller-supplied backend has no bias sets"; return DSM_ERR_STATE; }
+  WChannel& c = w->ch[slot];
+  if (!c.open || c.in_closed) { w->err = "channel is closed"; return DSM_ERR_STATE; }
+#ifndef DSM_HOST_ONLY
+  if (int rc = dsm_asr_set_bias(w->eng, slot, set)) { w->err = dsm_last_error(w->eng); return rc; }
+#endif
+  c.bias_set = set;
   return 0;
 }
 
@@ -660,7 +682,16 @@ int dsm_worker_step_encode(dsm_worker* w) {
     const int bid = w->active[i];
     WChannel& c = w->ch[bid];
     if (!c.open || c.out_closed) {
+#ifndef DSM_HOST_ONLY
+      // dsm_worker_set_bias: the next channel of this slot starts unbiased.  The call waits for the model and group streams
+      // (this is the encoder thread, and w->mu is held: the model thread takes it only outside its engine calls, so it cannot
+      // be waiting for us).  Frames of this slot that the run-ahead pipeline still holds then step detached: their output goes
+      // to a channel that is closed.  A failure is the step's failure; the channel stays listed and the detach is tried again.
+      if (c.bias_set && w->eng)
+        if (int brc = dsm_asr_set_bias(w->eng, bid, 0)) { w->err = dsm_last_error(w->eng); return brc; }
+#endif
       c.open = false;
+      c.bias_set = 0;
       w->active.erase(w->active.begin() + (long)i);
       w->free_slots.push_back(bid);
     } else {

@@ -891,6 +891,73 @@ typedef int (*dsm_opus_decode_fn)(void* user, int slot, const uint8_t* packet, s
  * `slot` tells the callback which per-socket decoder state to use.  It must not call back into dsm_worker_* for the same slot. */
 void dsm_worker_set_opus_decoder(dsm_worker*, dsm_opus_decode_fn, void* user);
 
+/* ---- text bias: per-stream keyword boosting and token bias (this project's own; the reference takes the arg-max or the Gumbel
+ * sample of the raw row and stops, core/asr.rs:208-216).  Off by default: a step then enqueues exactly what it enqueues without
+ * this section.  Definition (csrc/dsm_text_bias.h, bit-identical on host and device): a BIAS SET holds token biases — (token,
+ * bias), bias finite or -inf (a ban) — and keywords, each ONE word as its piece ids with a boost > 0 in logit units, compiled
+ * into a trie.  A slot carries the set it is attached to (0 = none) and a trie node (0 the root, DSM_BIAS_DEAD outside the trie
+ * or where the engine cannot know the position).  The step's pick runs on x = raw logits + token biases + the boosts of the
+ * node's edges (two f32 adds in that order), then the node advances: token 0 or 3 -> root, else along the token, else DEAD.
+ * The raw logits are not modified: "lm.logits", the token scores and the extra heads see what they see without this section.
+ * Greedy shallow fusion: a partial match that then fails is not taken back; multi-word phrases are out of scope.
+ *   dsm_asr_set_text_bias   engine-wide switch; on: lm_pick_biased_kernel picks every slot's token (one launch in place of the
+ *     arg-max / Gumbel launch, none added).  Any time between steps; waits for calls in progress on other threads; a change makes
+ *     the LM step's graphs settle again (two eager steps).  DSM_ERR_INVALID when text_out_vocab_size is above 15360 (the row is
+ *     staged in LDS) or below 4.  Turning it off keeps sets and attachments; turning it on puts every attached slot's node at
+ *     the root (never stepped) or DEAD.
+ *   dsm_asr_bias_create     compiles and uploads a set (one device allocation); *set_out is a positive handle, never reused in
+ *     the engine's life.  DSM_ERR_INVALID — engine unchanged — for more than DSM_BIAS_MAX_TOKENS token biases, a token >=
+ *     text_out_vocab_size or listed twice, a bias that is +inf or NaN, a keyword of 0 or more than DSM_BIAS_MAX_KEYWORD_TOKENS
+ *     pieces, a piece >= text_out_vocab_size or equal to 0 / 3, a boost that is not finite and > 0, more than DSM_BIAS_MAX_NODES
+ *     trie nodes; DSM_ERR_STATE when DSM_BIAS_MAX_SETS - 1 sets exist.
+ *   dsm_asr_bias_create_text  the same with the keywords as UTF-8 words: each is encoded alone with dsm_spm_encode.  A word is
+ *     refused by index in dsm_last_error when it contains whitespace, encodes to nothing or to more than 32 pieces, or yields a
+ *     piece >= text_out_vocab_size or equal to 0 / 3.  (The pieces a checkpoint emits for a word may differ from the tokenizer's
+ *     best segmentation: DESIGN.md.)
+ *   dsm_asr_bias_destroy    DSM_ERR_STATE ("in use by n slots") while attached; dsm_destroy frees what is left.
+ *   dsm_asr_bias_info       nodes, edges, token biases, current references, device bytes; any pointer may be NULL.
+ *   dsm_asr_set_bias        attaches `slot` to `set` (0 detaches), whether the switch is on or off.  Synchronises the engine's
+ *     streams.  The node becomes the root if the slot has not stepped since its last reset (host step index 0), else DEAD, which
+ *     heals at the stream's next 0 / 3.  dsm_asr_reset_slot keeps the attachment and returns the node to the root.  Slot
+ *     snapshots do not carry either: after dsm_asr_import_slots / dsm_asr_move_slots the destination keeps ITS OWN attachment and
+ *     its node is DEAD, or the root when the imported item's step index is 0; the blob's bytes do not depend on this section.
+ *   dsm_asr_bias_state      the slot's set and node as of the last finished step (synchronises).  Without a set the node reads DEAD.
+ *   dsm_text_bias_compile   host only, no device: the flat table of a set.  *needed (optional) receives its length in words;
+ *     words_out NULL: size query only; cap < needed: DSM_ERR_INVALID.  dsm_last_error(NULL) is the calling thread's message.
+ *   dsm_text_bias_pick_host host only: the definition for one row — token and next node.  table NULL (table_words 0): no set,
+ *     the node comes back unchanged.  The table is checked in full first; DSM_ERR_INVALID for a malformed one, a table that names
+ *     a token >= V, a node that is neither DEAD nor below its node count, temperature > 0 with a NULL key or a position that is
+ *     not a multiple of 16.
+ *   dsm_debug_text_pick     test aid: runs the step's KERNEL on caller rows — host logits [n][V], nodes_in [n], for temperature > 0
+ *     rng_keys [n][8] and rng_pos [n]; tokens_out [n], nodes_out [n].  `set` 0: no set.  4 <= V <= 15360 and above every token
+ *     of the set.  Synchronises the model stream.
+ *   dsm_worker_set_bias     dsm_asr_set_bias for an open channel's slot; the worker detaches the slot when the channel closes
+ *     (in the dsm_worker_step_encode that recycles the slot; frames of it still in the run-ahead pipeline then step detached)
+ *     and, for channels still open, in dsm_worker_destroy — which therefore comes before dsm_destroy of the engine.
+ *     DSM_ERR_STATE for a closed channel or a worker built with dsm_worker_create_with_backend.  The wire format does not change. */
+#define DSM_BIAS_MAX_TOKENS 1024
+#define DSM_BIAS_MAX_KEYWORD_TOKENS 32
+#define DSM_BIAS_MAX_NODES 65535
+#define DSM_BIAS_MAX_SETS 256
+#define DSM_BIAS_DEAD 0xFFFFFFFFu
+typedef struct { uint32_t token; float bias; } dsm_bias_token;
+typedef struct { const uint32_t* tokens; int n_tokens; float boost; } dsm_bias_keyword;
+int dsm_asr_set_text_bias(dsm_engine*, int on);
+int dsm_asr_bias_create(dsm_engine*, const dsm_bias_token*, int n_tokens, const dsm_bias_keyword*, int n_keywords, int* set_out);
+int dsm_asr_bias_create_text(dsm_engine*, const dsm_spm*, const char* const* words, const float* boosts, int n_words,
+                             const dsm_bias_token*, int n_tokens, int* set_out);
+int dsm_asr_bias_destroy(dsm_engine*, int set);
+int dsm_asr_bias_info(dsm_engine*, int set, int* nodes, int* edges, int* tokens, int* refs, size_t* device_bytes);
+int dsm_asr_set_bias(dsm_engine*, int slot, int set /* 0 detaches */);
+int dsm_asr_bias_state(dsm_engine*, int slot, int* set, uint32_t* node);
+int dsm_text_bias_compile(const dsm_bias_token* tokens, int n_tokens, const dsm_bias_keyword* keywords, int n_keywords, int V,
+                          uint32_t* words_out, size_t cap, size_t* needed);
+int dsm_text_bias_pick_host(const uint32_t* table, size_t table_words, uint32_t node, const float* logits, int V, float temperature,
+                            const uint32_t* rng_key /*8 words or NULL*/, uint64_t rng_pos, uint32_t* token, uint32_t* node_out);
+int dsm_debug_text_pick(dsm_engine*, int set, const float* logits, int n, int V, const uint32_t* nodes_in, float temperature,
+                        const uint32_t* rng_keys /*[n][8] or NULL*/, const uint64_t* rng_pos, uint32_t* tokens_out, uint32_t* nodes_out);
+int dsm_worker_set_bias(dsm_worker*, int slot, int set);
+
 #ifdef __cplusplus
 }
 #endif
