@@ -157,7 +157,7 @@ ABI_SYMBOLS = [
     "dsm_spm_load", "dsm_spm_load_bytes", "dsm_spm_free", "dsm_spm_last_error", "dsm_spm_vocab_size", "dsm_spm_special_ids",
     "dsm_spm_encode", "dsm_spm_decode", "dsm_worker_set_tokenizer_file",
     "dsm_tts_attach_tokenizer", "dsm_tts_request_push_text", "dsm_tts_word_text",
-    "dsm_tts_slot_blob_info",
+    "dsm_tts_slot_blob_info", "dsm_tts_slot_layout",
     "dsm_asr_set_token_scores", "dsm_asr_token_scores", "dsm_asr_token_scores_dev", "dsm_asr_poll_word_scores",
     "dsm_token_scores_host", "dsm_debug_token_scores", "dsm_worker_set_word_scores",
     "dsm_asr_set_text_bias", "dsm_asr_bias_create", "dsm_asr_bias_create_text", "dsm_asr_bias_destroy", "dsm_asr_bias_info",
@@ -388,6 +388,8 @@ def load_library(path=None):
     lib.dsm_tts_word_text.restype = C.c_int64
     lib.dsm_tts_slot_blob_info.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(TtsSlotBlobInfo)]
     lib.dsm_tts_slot_blob_info.restype = C.c_int
+    lib.dsm_tts_slot_layout.argtypes = [C.POINTER(TtsConfig), C.POINTER(MimiConfig), C.c_char_p, C.c_size_t]
+    lib.dsm_tts_slot_layout.restype = C.c_int
     lib.dsm_asr_set_token_scores.argtypes = [vp, C.c_int]
     lib.dsm_asr_token_scores.argtypes = [vp, fp, u32p, fp]
     lib.dsm_asr_token_scores_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
@@ -534,6 +536,30 @@ def slot_blob_info(blob):
 def tts_slot_blob_info(blob):
     """dsm_tts_slot_blob_info: header fields of a TTS slot blob as a dict (host only, no device); DsmError for a malformed one."""
     return _blob_info(blob, TtsSlotBlobInfo(), "dsm_tts_slot_blob_info", "dsm_tts_last_error")
+
+
+def tts_slot_layout(cfg, mimi_cfg=None):
+    """dsm_tts_slot_layout: the device payload of a TTS slot blob for a configuration (host only, no device) as
+    {"sections": [(name, bytes_per_slot, payload_offset), ...], "slot_bytes": int, "signature": [int, ...]};
+    mimi_cfg None: without the Mimi decode group."""
+    lib = load_library()
+    mp = C.byref(mimi_cfg) if mimi_cfg is not None else None
+    n = lib.dsm_tts_slot_layout(C.byref(cfg), mp, None, 0)
+    if n < 0:
+        msg = lib.dsm_tts_last_error(None)
+        raise DsmError(f"dsm error {n}: {msg.decode() if msg else '?'}")
+    buf = C.create_string_buffer(n + 1)
+    lib.dsm_tts_slot_layout(C.byref(cfg), mp, buf, n + 1)
+    out = {"sections": [], "slot_bytes": None, "signature": None}
+    for line in buf.value.decode().splitlines():
+        f = line.split()
+        if f[0] == "slot_bytes":
+            out["slot_bytes"] = int(f[1])
+        elif f[0] == "signature":
+            out["signature"] = [int(w) for w in f[1:]]
+        else:
+            out["sections"].append((f[0], int(f[1]), int(f[2])))
+    return out
 
 
 def token_scores_host(logits, token, top_n=0):

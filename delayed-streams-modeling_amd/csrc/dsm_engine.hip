@@ -31,6 +31,7 @@
 #include "dsm_safetensors.h"
 #include "dsm_slot_blob.h"
 #include "dsm_tts_slot_blob.h"
+#include "dsm_tts_slot_layout.h"
 #include "dsm_spm.h"
 #include "dsm_slot_xfer.inc"
 

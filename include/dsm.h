@@ -470,15 +470,21 @@ int dsm_tts_set_voice(dsm_tts*, int slot, int voice, int voice_uncond /* 0 = no 
  * aligned sections, a signature of every configuration field that fixes a size or a meaning, an importer that never reads an
  * offset from the blob — with a magic of its own: dsm_slot_blob_info and dsm_asr_import_slots refuse a TTS blob with "bad
  * magic", and dsm_tts_slot_blob_info refuses an STT blob the same way.  The engine calls that fill and consume such a blob
- * (export, import, move) are NOT in the library yet: only the format, its writer and its checked reader are.
+ * (export, import, move) are NOT in the library yet: only the format, its writer, its checked reader and the payload's layout are.
  *   dsm_tts_slot_blob_info  host only, no device needed: checks header and host section (every count against its bound, the
- *     sizes against each other and against `len`), fills *out.  DSM_ERR_INVALID with dsm_tts_last_error(NULL) naming the fault. */
+ *     sizes against each other and against `len`), fills *out.  DSM_ERR_INVALID with dsm_tts_last_error(NULL) naming the fault.
+ *   dsm_tts_slot_layout     host only, no device, pure: the device payload's section list for a configuration (mimi NULL:
+ *     without the Mimi decode group) as text, one line per section "name bytes_per_slot payload_offset", then "slot_bytes N"
+ *     and "signature w0 w1 ...".  Returns the text's length; the text is written (NUL-terminated) when cap is larger.
+ *     DSM_ERR_INVALID, dsm_tts_last_error(NULL), for a configuration no engine can have.  csrc/dsm_tts_slot_layout.h, which
+ *     also holds the index checks an import has to make before it writes (tests/sanitize_tts_xfer/ runs them under sanitizers). */
 #define DSM_TTS_SLOT_BLOB_HAS_MIMI_DEC 1u
 struct dsm_tts_slot_blob_info {
   uint32_t version, n_slots, flags, sig_words, slices /* dep_num_slices */, reserved;
   uint64_t host_bytes, slot_bytes, total_bytes; /* host section, device payload per slot, the whole blob */
 };
 int dsm_tts_slot_blob_info(const void* buf, size_t len, struct dsm_tts_slot_blob_info* out);
+int dsm_tts_slot_layout(const dsm_tts_config*, const dsm_mimi_config* /* NULL: no decode group */, char* buf, size_t cap);
 /* Generated frames to PCM — what the reference's TTS worker does with every step's tokens: a second thread receives
  * state.last_audio_tokens() and runs Mimi::decode_step on them (srv/tts.rs:528-544, core/mimi.rs:217-225) while the inference
  * loop is already in its next step.
