@@ -163,7 +163,13 @@ ABI_SYMBOLS = [
     "dsm_asr_set_text_bias", "dsm_asr_bias_create", "dsm_asr_bias_create_text", "dsm_asr_bias_destroy", "dsm_asr_bias_info",
     "dsm_asr_set_bias", "dsm_asr_bias_state", "dsm_text_bias_compile", "dsm_text_bias_pick_host", "dsm_debug_text_pick",
     "dsm_worker_set_bias",
+    "dsm_asr_set_ingest", "dsm_asr_set_input_format", "dsm_asr_input_format", "dsm_mimi_encode_step_raw",
+    "dsm_mimi_encode_step_raw_async", "dsm_mimi_encode_step_raw_dev", "dsm_asr_step_raw", "dsm_debug_ingest_read",
+    "dsm_ingest_host_new", "dsm_ingest_host_free", "dsm_ingest_host", "dsm_ingest_describe", "dsm_ingest_g711_table",
+    "dsm_worker_set_input_rate",
 ]
+PCM_F32, PCM_S16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3  # DSM_PCM_*: the sample formats of the ingest section
+INGEST_MAX_FRAME_BYTES = 15360  # the largest raw frame (48 kHz f32) and the largest pitch of the raw calls
 BIAS_MAX_TOKENS, BIAS_MAX_KEYWORD_TOKENS, BIAS_MAX_NODES, BIAS_MAX_SETS = 1024, 32, 65535, 256  # DSM_BIAS_MAX_*
 BIAS_DEAD = 0xFFFFFFFF  # DSM_BIAS_DEAD: the trie node of a slot inside a word that left the trie
 
@@ -419,6 +425,27 @@ def load_library(path=None):
         getattr(lib, name).restype = C.c_int
     for name in ("dsm_tts_create", "dsm_tts_step", "dsm_tts_audio_tokens", "dsm_tts_step_idx", "dsm_tts_reset_slot",
                  "dsm_tts_debug_read"):
+        getattr(lib, name).restype = C.c_int
+    intp = C.POINTER(C.c_int)
+    lib.dsm_asr_set_ingest.argtypes = [vp, C.c_int]
+    lib.dsm_asr_set_input_format.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.dsm_asr_input_format.argtypes = [vp, C.c_int] + [intp] * 5
+    lib.dsm_mimi_encode_step_raw.argtypes = [vp, vp, C.c_size_t, vp, u32p, intp]
+    lib.dsm_mimi_encode_step_raw_async.argtypes = [vp, vp, C.c_size_t, vp, intp]
+    lib.dsm_mimi_encode_step_raw_dev.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    lib.dsm_asr_step_raw.argtypes = [vp, vp, C.c_size_t, vp, u32p, u32p, fp]
+    lib.dsm_debug_ingest_read.argtypes = [vp, C.c_int, fp]
+    lib.dsm_ingest_host_new.argtypes = [C.c_int, C.c_int]
+    lib.dsm_ingest_host_new.restype = C.c_void_p
+    lib.dsm_ingest_host_free.argtypes = [vp]
+    lib.dsm_ingest_host_free.restype = None
+    lib.dsm_ingest_host.argtypes = [vp, vp, fp]
+    lib.dsm_ingest_describe.argtypes = [C.c_int, C.c_int, u32p]
+    lib.dsm_ingest_g711_table.argtypes = [C.c_int, C.POINTER(C.c_int16)]
+    lib.dsm_worker_set_input_rate.argtypes = [vp, C.c_int, C.c_int]
+    for name in ("dsm_asr_set_ingest", "dsm_asr_set_input_format", "dsm_asr_input_format", "dsm_mimi_encode_step_raw",
+                 "dsm_mimi_encode_step_raw_async", "dsm_mimi_encode_step_raw_dev", "dsm_asr_step_raw", "dsm_debug_ingest_read",
+                 "dsm_ingest_host", "dsm_ingest_describe", "dsm_ingest_g711_table", "dsm_worker_set_input_rate"):
         getattr(lib, name).restype = C.c_int
     if path is None:
         _lib = lib
@@ -825,6 +852,16 @@ class Worker:
             e.code = rc
             raise e
 
+    def set_input_rate(self, slot, hz):
+        """dsm_worker_set_input_rate: the open channel's Audio samples are f32 at `hz` from now on (set before its first audio);
+        its queue is cut into frames of 2 hz / 25 samples and resampled on the device.  24000 again when the channel closes.
+        Engine-backed workers only."""
+        rc = self.lib.dsm_worker_set_input_rate(self.h, int(slot), int(hz))
+        if rc < 0:
+            e = DsmError(f"dsm error {rc}: {self._err()}")
+            e.code = rc
+            raise e
+
     def set_bias(self, slot, handle):
         """dsm_worker_set_bias: attach an open channel's slot to a bias set of the engine (0 detaches); the worker detaches it
         when the channel closes.  Engine-backed workers only."""
@@ -972,6 +1009,65 @@ def wav_decode(data):
         return np.ctypeslib.as_array(ptr, shape=(n.value,)).copy() if n.value else np.zeros(0, np.float32), rate.value
     finally:
         lib.dsm_free(ptr)
+
+
+def ingest_describe(rate, fmt):
+    """dsm_ingest_describe: the descriptor of an input format (csrc/dsm_ingest.h) as a dict — rate, fmt, L, M, half, taps, F_in,
+    frame_bytes, D (the latency in 24 kHz samples), table_words.  DsmError with the reason for a rate or format outside the
+    definition."""
+    lib = load_library()
+    w = np.zeros(12, dtype=np.uint32)
+    rc = lib.dsm_ingest_describe(int(rate), int(fmt), _ptr(w))
+    if rc != 0:
+        msg = lib.dsm_last_error(None)
+        raise DsmError(f"dsm_ingest_describe failed ({rc}): {msg.decode() if msg else '?'}")
+    names = ("rate", "fmt", "L", "M", "half", "taps", "F_in", "frame_bytes", "D", "table_off", "table_words", "reserved")
+    return {k: int(v) for k, v in zip(names, w) if k not in ("table_off", "reserved")}
+
+
+def ingest_g711_table(fmt):
+    """The 256 expanded 16-bit values of PCM_MULAW / PCM_ALAW (int16 array), as the engine's tables are built."""
+    out = np.zeros(256, dtype=np.int16)
+    if load_library().dsm_ingest_g711_table(int(fmt), out.ctypes.data_as(C.POINTER(C.c_int16))) != 0:
+        raise DsmError("dsm_ingest_g711_table: the format is neither mu-law nor A-law")
+    return out
+
+
+class ingest_host:
+    """dsm_ingest_host_*: one slot's streaming ingest on the host — the function ingest_resample_kernel is bit-identical to.
+    step(raw) takes one frame (bytes, or an array whose bytes are the frame: frame_bytes of them) and returns the 1920 samples
+    at 24 kHz the step hands Mimi."""
+
+    def __init__(self, rate, fmt=PCM_F32):
+        self.lib = load_library()
+        self.info = ingest_describe(rate, fmt)  # raises with the reason for an unsupported format
+        self.frame_samples, self.frame_bytes, self.latency = self.info["F_in"], self.info["frame_bytes"], self.info["D"]
+        self.h = self.lib.dsm_ingest_host_new(int(rate), int(fmt))
+        if not self.h:
+            msg = self.lib.dsm_last_error(None)
+            raise DsmError(f"dsm_ingest_host_new failed: {msg.decode() if msg else '?'}")
+
+    def step(self, raw):
+        raw = raw if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw).tobytes()
+        if len(raw) != self.frame_bytes:
+            raise DsmError(f"ingest_host.step: a frame of {len(raw)} bytes, the format's frame has {self.frame_bytes}")
+        out = np.zeros(FRAME_SIZE, dtype=np.float32)
+        rc = self.lib.dsm_ingest_host(self.h, bytes(raw), _ptr(out))
+        if rc != 0:
+            msg = self.lib.dsm_last_error(None)
+            raise DsmError(f"dsm_ingest_host failed ({rc}): {msg.decode() if msg else '?'}")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.dsm_ingest_host_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class LinearResampler:
@@ -1251,6 +1347,72 @@ class AsrEngine:
         out = np.zeros(n, dtype=np.float32)
         got = self._check(self.lib.dsm_debug_read(self.h, name.encode(), _ptr(out), n))
         return out[:got]
+
+    # ingest (include/dsm.h "ingest"): per-slot input sample rate and sample format, resampled on the device
+    def set_ingest(self, on):
+        """dsm_asr_set_ingest: the engine-wide switch; on allocates the section and lets the raw calls run."""
+        self._check(self.lib.dsm_asr_set_ingest(self.h, 1 if on else 0))
+
+    def set_input_format(self, slot, rate, fmt=PCM_F32):
+        """dsm_asr_set_input_format: the slot's format from its next frame on; clears its history on both Mimi sides."""
+        self._check(self.lib.dsm_asr_set_input_format(self.h, int(slot), int(rate), int(fmt)))
+
+    def input_format(self, slot):
+        """(rate, fmt, frame_samples, frame_bytes, latency in 24 kHz samples) of the slot."""
+        v = [C.c_int(0) for _ in range(5)]
+        self._check(self.lib.dsm_asr_input_format(self.h, int(slot), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _raw_rows(self, raw, pitch):
+        """raw: bytes / a uint8 array of B * pitch bytes, or a list of B per-slot frames (bytes or arrays) packed here."""
+        if isinstance(raw, (list, tuple)):
+            rows = np.zeros((self.B, pitch), dtype=np.uint8)
+            for b, r in enumerate(raw):
+                if r is None:
+                    continue
+                r = np.frombuffer(r if isinstance(r, (bytes, bytearray)) else np.ascontiguousarray(r).tobytes(), dtype=np.uint8)
+                if r.size > pitch:
+                    raise DsmError(f"slot {b}'s frame has {r.size} bytes, the pitch is {pitch}")
+                rows[b, :r.size] = r
+            return rows
+        rows = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+        if rows.size != self.B * pitch:
+            raise DsmError(f"raw rows: {rows.size} bytes, B x pitch is {self.B * pitch}")
+        return np.ascontiguousarray(rows)
+
+    def encode_step_raw(self, raw, mask, pitch=INGEST_MAX_FRAME_BYTES):
+        rows = self._raw_rows(raw, pitch)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        codes = np.zeros((self.B, self.n_q), dtype=np.uint32)
+        produced = C.c_int(0)
+        self._check(self.lib.dsm_mimi_encode_step_raw(self.h, _ptr(rows), pitch, _ptr(mask), _ptr(codes), C.byref(produced)))
+        return codes if produced.value else None
+
+    def encode_step_raw_async(self, raw, mask, pitch=INGEST_MAX_FRAME_BYTES):
+        rows = self._raw_rows(raw, pitch)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        ticket = C.c_int(-1)
+        self._check(self.lib.dsm_mimi_encode_step_raw_async(self.h, _ptr(rows), pitch, _ptr(mask), C.byref(ticket)))
+        return ticket.value
+
+    def encode_step_raw_dev(self, d_raw, pitch, d_mask, d_codes):
+        self._check(self.lib.dsm_mimi_encode_step_raw_dev(self.h, d_raw, pitch, d_mask, d_codes))
+
+    def step_raw(self, raw, mask, pitch=INGEST_MAX_FRAME_BYTES):
+        rows = self._raw_rows(raw, pitch)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        codes = np.zeros((self.B, self.n_q), dtype=np.uint32)
+        text = np.zeros(self.B, dtype=np.uint32)
+        nh = self.cfg.extra_heads_num
+        prs = np.zeros((max(nh, 1), self.B), dtype=np.float32)
+        self._check(self.lib.dsm_asr_step_raw(self.h, _ptr(rows), pitch, _ptr(mask), _ptr(codes), _ptr(text), _ptr(prs) if nh else None))
+        return codes, text, prs[:nh]
+
+    def debug_ingest_read(self, side=0):
+        """The frames [B][1920] the side's (0 encoder, 1 model) last raw call handed to Mimi."""
+        out = np.zeros((self.B, FRAME_SIZE), dtype=np.float32)
+        self._check(self.lib.dsm_debug_ingest_read(self.h, int(side), _ptr(out)))
+        return out
 
     # device-pointer variants (ints from torch.Tensor.data_ptr())
     def encode_step_dev(self, d_pcm, d_mask, d_codes):

@@ -18,6 +18,7 @@
 #include "dsm_sampling.h"
 #include "dsm_token_scores.h"
 #include "dsm_text_bias.h"
+#include "dsm_ingest.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short dsm_bf16x8 __attribute__((ext_vector_type(8)));
@@ -3095,4 +3096,46 @@ __global__ void spk_pad_rows_kernel(float* __restrict__ rows, const float* __res
 __global__ void fill_u32_kernel(uint32_t* p, uint32_t v, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------
+// Ingest (dsm_ingest.h; this project's own, off by default): a slot's raw frame — its own sample rate and sample format — to the
+// 1920 samples at 24 kHz of the step, written where upload_pcm's 2-D copy writes them: MimiState::pcm at the init conv's pitch.
+// One 256-thread workgroup per slot.  The slot's history and its decoded frame are staged in dynamic LDS as f32 (at most
+// 136 + 3840 floats); each thread walks outputs n = tid, tid + 256, ... with the serial fp64 chain of dsm_ingest_output (a product
+// of two floats is exact in double: v_fma_f64 gives the host's multiply-add bits); then the frame's last `taps` samples become
+// the history.  A masked-off slot returns at once: nothing read, nothing written.  Every index is bounded by the descriptor,
+// which the engine admits through dsm_ingest::check only: LDS taps + F_in <= 3976 floats, coefficient reads inside the table.
+// ------------------------------------------------------------------------------------------
+struct IngestArgs {
+  const uint8_t* raw;           // [B][pitch] bytes
+  size_t pitch;
+  const uint8_t* mask;          // [B]
+  const uint32_t* slot_desc;    // [B] index into descs
+  const dsm_ingest_desc* descs;
+  const float* coef;            // the coefficient arena
+  const float* g711;            // [2][256]
+  float* hist;                  // [B][DSM_INGEST_MAX_TAPS]
+  uint32_t* started;            // [B]
+  float* pcm;                   // slot 0's frame; slots are pcm_pitch floats apart
+  long pcm_pitch;
+};
+
+constexpr size_t ingest_lds() { return sizeof(float) * (DSM_INGEST_MAX_TAPS + DSM_INGEST_MAX_FRAME); }
+__global__ __launch_bounds__(256) void ingest_resample_kernel(IngestArgs a) {
+  extern __shared__ float ingest_buf[];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (!a.mask[b]) return;
+  const dsm_ingest_desc d = a.descs[a.slot_desc[b]];
+  const uint8_t* row = a.raw + (size_t)b * a.pitch;
+  float* out = a.pcm + (long)b * a.pcm_pitch;
+  float* hist = a.hist + (size_t)b * DSM_INGEST_MAX_TAPS;
+  const uint32_t started = a.started[b];
+  for (uint32_t i = tid; i < d.taps; i += 256) ingest_buf[i] = started ? hist[i] : 0.0f;
+  for (uint32_t i = tid; i < d.F_in; i += 256) ingest_buf[d.taps + i] = dsm_unpaired(dsm_ingest_decode(d.fmt, row, i, a.g711));
+  __syncthreads();
+  const float* coef = a.coef + d.table_off;
+  for (int n = tid; n < DSM_FRAME_SIZE; n += 256) out[n] = dsm_ingest_output(&d, coef, ingest_buf, started, n);
+  for (uint32_t i = tid; i < d.taps; i += 256) hist[i] = ingest_buf[d.F_in + i];  // LDS is read-only since the barrier
+  if (tid == 0) a.started[b] = 1u;
 }

@@ -13,6 +13,7 @@
 // Not built: MPEG-2 / 2.5 (LSF) streams, Layers I / II, free-format bit rates, CRC verification (the check word is skipped).
 // Intensity stereo follows the standard's text but no sample exercises it (all five files are mono).
 #include <math.h>
+#include "dsm_ingest.h"  // guarded: the phase table of the resampler, shared with the per-slot ingest
 
 namespace dsm_mp3 {
 
@@ -549,36 +550,16 @@ static int decode_stream(const uint8_t* b, size_t len, std::vector<float>* left,
 // cut-off at 0.5 min(rate_in, rate_out) x 0.95.  kaudio is an un-vendored crate (it wraps a sinc resampler of the same family);
 // its coefficients are not reproduced — parity unpinned, the properties are tested (DC gain, a tone keeps its frequency and
 // level, images below -80 dB).
-static double bessel_i0(double x) {
-  double s = 1.0, t = 1.0;
-  for (int k = 1; k < 64; ++k) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; if (t < 1e-18 * s) break; }
-  return s;
-}
-
+// The phase table (Kaiser beta 8.6, per-phase normalisation, stored as float) is dsm_ingest::phase_table (dsm_ingest.h), shared
+// with the streaming per-slot ingest, whose definition is this function's output cut into frames.
 static int resample(const float* in, size_t n, int rin, int rout, std::vector<float>* out) {
   if (rin <= 0 || rout <= 0) return -1;
   if (rin == rout) { out->assign(in, in + n); return 0; }
-  auto gcd = [](long a, long b) { while (b) { const long t = a % b; a = b; b = t; } return a; };
-  const long g = gcd(rin, rout), L = rout / g, M = rin / g;
-  if (L > 4096) return -1;  // the phase table would be unreasonable: not a ratio between audio rates
-  const int Z = 32;
-  const double fc = 0.95 * (rout < rin ? (double)rout / rin : 1.0);  // relative to the input's Nyquist
-  const int half = (int)ceil(Z / fc);
+  long L = 0, M = 0;
+  int half = 0;
+  std::vector<float> ph;
+  if (dsm_ingest::phase_table(rin, rout, &L, &M, &half, &ph)) return -1;
   const int taps = 2 * half;
-  const double beta = 8.6, i0b = bessel_i0(beta);
-  std::vector<float> ph((size_t)L * taps);
-  for (long p = 0; p < L; ++p) {  // phase p: fractional position p / L past the integer input index
-    double sum = 0.0;
-    for (int k = 0; k < taps; ++k) {
-      const double t = (k - half + 1) - (double)p / L;  // distance (input samples) from the output instant to tap k
-      const double x = M_PI * fc * t;
-      const double w = fabs(t) < half ? bessel_i0(beta * sqrt(1.0 - (t / half) * (t / half))) / i0b : 0.0;
-      const double v = fc * (fabs(x) < 1e-12 ? 1.0 : sin(x) / x) * w;
-      ph[(size_t)p * taps + k] = (float)v;
-      sum += v;
-    }
-    for (int k = 0; k < taps; ++k) ph[(size_t)p * taps + k] = (float)(ph[(size_t)p * taps + k] / sum);  // unit DC gain per phase
-  }
   const size_t nout = (size_t)(((unsigned long long)n * (unsigned long long)L + M - 1) / M);
   out->resize(nout);
   for (size_t j = 0; j < nout; ++j) {

@@ -230,6 +230,10 @@ struct WChannel {  // srv/batched_asr.rs:69-116
   std::deque<float> data;
   size_t steps = 0;
   int bias_set = 0;  // dsm_worker_set_bias: what the channel's slot is attached to; detached when the channel closes
+  // dsm_worker_set_input_rate: the rate of the channel's Audio samples and its frame of 80 ms in them; back to 24000 / 1920 when
+  // the channel closes
+  int rate = 24000;
+  size_t frame = DSM_FRAME_SIZE;
 };
 
 }  // namespace
@@ -243,6 +247,7 @@ struct dsm_worker {
   uint64_t next_channel_id = 1, marker_seq = 0;
   size_t enc_step_idx = 0, model_step_idx = 0;
   std::vector<float> batch_pcm;
+  std::vector<float> batch_raw;  // [B][48 kHz frame]: in being once a channel has a rate of its own; a step uses it at that step's pitch
   std::vector<uint8_t> mask;
   std::vector<uint64_t> channel_ids;  // 0 = None
   std::deque<WPipelineMsg> pipe;      // encoder_loop -> model_loop (sync_channel, srv/batched_asr.rs:291)
@@ -256,17 +261,18 @@ struct dsm_worker {
   std::mutex mu;
   std::string err;
 
-  bool extend_data(WChannel& c, const float* pcm, size_t n, float* out_pcm) {  // Channel::extend_data
-    if (n == 0 && c.data.size() < DSM_FRAME_SIZE) return false;
-    if (c.data.empty() && n >= DSM_FRAME_SIZE) {
-      memcpy(out_pcm, pcm, sizeof(float) * DSM_FRAME_SIZE);
-      c.data.insert(c.data.end(), pcm + DSM_FRAME_SIZE, pcm + n);
+  bool extend_data(WChannel& c, const float* pcm, size_t n, float* out_pcm) {  // Channel::extend_data, in frames of the channel's rate
+    const size_t F = c.frame;
+    if (n == 0 && c.data.size() < F) return false;
+    if (c.data.empty() && n >= F) {
+      memcpy(out_pcm, pcm, sizeof(float) * F);
+      c.data.insert(c.data.end(), pcm + F, pcm + n);
       return true;
     }
     c.data.insert(c.data.end(), pcm, pcm + n);
-    if (c.data.size() >= DSM_FRAME_SIZE) {
-      std::copy(c.data.begin(), c.data.begin() + DSM_FRAME_SIZE, out_pcm);
-      c.data.erase(c.data.begin(), c.data.begin() + DSM_FRAME_SIZE);
+    if (c.data.size() >= F) {
+      std::copy(c.data.begin(), c.data.begin() + (long)F, out_pcm);
+      c.data.erase(c.data.begin(), c.data.begin() + (long)F);
       return true;
     }
     return false;
@@ -422,6 +428,9 @@ void dsm_worker_destroy(dsm_worker* w) {
   // dsm_worker_set_bias: what the worker attached it detaches, so that the engine's owner can destroy the sets
   for (int b = 0; b < w->B && w->eng; ++b)
     if (w->ch[(size_t)b].bias_set) (void)dsm_asr_set_bias(w->eng, b, 0);
+  // dsm_worker_set_input_rate: the slots go back to 24 kHz, so that the engine's owner finds them as the worker found them
+  for (int b = 0; b < w->B && w->eng; ++b)
+    if (w->ch[(size_t)b].rate != 24000) (void)dsm_asr_set_input_format(w->eng, b, 24000, DSM_PCM_F32);
 #endif
   delete w;
 }
@@ -471,6 +480,28 @@ int dsm_worker_set_bias(dsm_worker* w, int slot, int set) {
   if (int rc = dsm_asr_set_bias(w->eng, slot, set)) { w->err = dsm_last_error(w->eng); return rc; }
 #endif
   c.bias_set = set;
+  return 0;
+}
+
+int dsm_worker_set_input_rate(dsm_worker* w, int slot, int hz) {
+  if (!w || slot < 0 || slot >= w->B) return DSM_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (!w->eng) { w->err = "an input rate needs the engine as backend (dsm_worker_create): a caller-supplied backend takes 24 kHz"; return DSM_ERR_STATE; }
+  WChannel& c = w->ch[slot];
+  if (!c.open || c.in_closed) { w->err = "channel is closed"; return DSM_ERR_STATE; }
+  if (hz == c.rate) return 0;
+  // samples already queued or cut were counted in frames of the old rate
+  if (!c.data.empty() || c.steps) { w->err = "the input rate is set before the channel's first audio is cut into frames"; return DSM_ERR_STATE; }
+#ifndef DSM_HOST_ONLY
+  dsm_ingest_desc d;
+  std::string derr;
+  if (int rc = dsm_ingest::describe(hz, DSM_PCM_F32, &d, &derr)) { w->err = derr; return rc; }
+  if (int rc = dsm_asr_set_ingest(w->eng, 1)) { w->err = dsm_last_error(w->eng); return rc; }  // a no-op once it is on
+  if (int rc = dsm_asr_set_input_format(w->eng, slot, hz, DSM_PCM_F32)) { w->err = dsm_last_error(w->eng); return rc; }
+  if (w->batch_raw.empty()) w->batch_raw.assign((size_t)w->B * DSM_INGEST_MAX_FRAME, 0.0f);
+  c.rate = hz;
+  c.frame = d.F_in;
+#endif
   return 0;
 }
 
@@ -644,11 +675,23 @@ int dsm_worker_step_encode(dsm_worker* w) {
   WPipelineMsg pm;
   std::fill(w->mask.begin(), w->mask.end(), 0);
   std::fill(w->channel_ids.begin(), w->channel_ids.end(), 0);
+  // dsm_worker_set_input_rate: while an open channel has a rate of its own the step goes through the raw entry point, every
+  // channel's frame — 1920 samples of a 24 kHz channel among them — in a row of the step's pitch: the longest open frame
+  size_t row = DSM_FRAME_SIZE;
+  bool raw = false;
+  for (int bid : w->active) {
+    const WChannel& c = w->ch[bid];
+    if (c.open && c.rate != 24000) raw = true;
+    if (c.open) row = std::max(row, c.frame);
+  }
+  if (!raw) row = DSM_FRAME_SIZE;
+  row = (row + 3) & ~(size_t)3;  // a pitch of whole 16 bytes
+  float* const batch = raw ? w->batch_raw.data() : w->batch_pcm.data();
   // ---- pre_process_pipelined — srv/batched_asr.rs:527-659 ----
   for (int bid : w->active) {
     WChannel& c = w->ch[bid];
-    float* out_pcm = &w->batch_pcm[(size_t)bid * DSM_FRAME_SIZE];
-    std::fill(out_pcm, out_pcm + DSM_FRAME_SIZE, 0.0f);
+    float* out_pcm = batch + (size_t)bid * row;
+    std::fill(out_pcm, out_pcm + row, 0.0f);
     if (!c.open) continue;
     w->channel_ids[bid] = c.id;
     if (c.out_closed) continue;
@@ -669,7 +712,9 @@ int dsm_worker_step_encode(dsm_worker* w) {
         encode_out(c.out.back(), ready);
         pm.resets.push_back(bid);
       } else if (m.kind == DSM_IN_MARKER) {
-        const size_t current_data = c.data.size() / DSM_FRAME_SIZE;
+        // queued frames in the channel's own frame length; a resampled channel's last D output samples in front of the marker
+        // land in the frame after, so its marker is due one step later
+        const size_t current_data = c.data.size() / c.frame + (c.rate != 24000 ? 1 : 0);
         pm.new_markers.push_back(WMarker{c.id, bid, w->enc_step_idx + (size_t)w->delay + current_data, m.id, w->marker_seq++});
       } else if (m.kind == DSM_IN_AUDIO) {
         if (w->extend_data(c, m.pcm.data(), m.pcm.size(), out_pcm)) { c.steps += 1; mask_val = true; }
@@ -689,7 +734,13 @@ int dsm_worker_step_encode(dsm_worker* w) {
       // to a channel that is closed.  A failure is the step's failure; the channel stays listed and the detach is tried again.
       if (c.bias_set && w->eng)
         if (int brc = dsm_asr_set_bias(w->eng, bid, 0)) { w->err = dsm_last_error(w->eng); return brc; }
+      // dsm_worker_set_input_rate: the next channel of this slot is a 24 kHz channel again (same place, same lock rules).  The
+      // slot is masked off in this step — a closed channel cuts no frame — so the step's raw rows do not hold a frame of it.
+      if (c.rate != 24000 && w->eng)
+        if (int irc = dsm_asr_set_input_format(w->eng, bid, 24000, DSM_PCM_F32)) { w->err = dsm_last_error(w->eng); return irc; }
 #endif
+      c.rate = 24000;
+      c.frame = DSM_FRAME_SIZE;
       c.open = false;
       c.bias_set = 0;
       w->active.erase(w->active.begin() + (long)i);
@@ -705,10 +756,14 @@ int dsm_worker_step_encode(dsm_worker* w) {
   pm.mask = w->mask;
   pm.ref_ids = w->channel_ids;
   for (int b = 0; b < B; ++b) pm.buffered.push_back(w->ch[b].data.size());
-  const std::vector<float> pcm = w->batch_pcm;  // the engine call runs outside the lock: a private copy of the frame
+  const std::vector<float> pcm(batch, batch + (size_t)B * row);  // the engine call runs outside the lock: a private copy of the frame
   lk.unlock();
   // ---- Mimi::encode_step — :351-377 ----
   int rc;
+#ifndef DSM_HOST_ONLY
+  if (raw) rc = dsm_mimi_encode_step_raw_async(w->eng, pcm.data(), sizeof(float) * row, pm.mask.data(), &pm.ticket);
+  else
+#endif
   if (be.encode_async) rc = be.encode_async(be.self, pcm.data(), pm.mask.data(), &pm.ticket);
   else rc = be.encode_step(be.self, pcm.data(), pm.mask.data());
   lk.lock();

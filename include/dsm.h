@@ -964,6 +964,69 @@ int dsm_debug_text_pick(dsm_engine*, int set, const float* logits, int n, int V,
                         const uint32_t* rng_keys /*[n][8] or NULL*/, const uint64_t* rng_pos, uint32_t* tokens_out, uint32_t* nodes_out);
 int dsm_worker_set_bias(dsm_worker*, int slot, int set);
 
+/* ---- ingest: per-stream input sample rate and sample format, resampled on the device (this project's own: the reference
+ * resamples request bodies only, srv/batched_asr.rs:835-838, and its sockets must send 24 kHz f32).  Off by default: nothing is
+ * allocated and every other call enqueues exactly what it enqueues without this section.  Definition (csrc/dsm_ingest.h,
+ * bit-identical on host and device): a slot's FORMAT is a sample rate — 8000 .. 48000 Hz with a whole number F_in = 2 rate / 25
+ * of samples per 80 ms frame (8000, 11025, 16000, 22050, 32000, 44100, 48000 among them) — and a sample format: DSM_PCM_F32,
+ * DSM_PCM_S16 (little endian, v / 32768), DSM_PCM_MULAW, DSM_PCM_ALAW (ITU-T G.711, expanded to 16 bits, then as s16).  With x
+ * the slot's decoded input since the format was set and y = dsm_resample(x, rate, 24000), step t hands Mimi
+ * z_t[n] = y[1920 t + n - D], 0 in front of the stream: D = floor(half L / M) output samples (102 at 8 kHz, 51 at 16 kHz, 33 at
+ * 44.1 kHz, 34 at 48 kHz; 0 at 24 kHz) is the format's latency.  24000 / F32 is the pass-through format and every slot's default.
+ *   dsm_asr_set_ingest        engine-wide switch.  On: allocates the section (per-slot format and history, the raw staging at the
+ *     largest pitch, 15360 bytes a slot) and lets the raw calls run; off: they return DSM_ERR_STATE.  The plain calls are the
+ *     same either way.  Formats and histories stay across off / on.
+ *   dsm_asr_set_input_format  sets the slot's format and clears its history on both Mimi sides (the next frame is the first of
+ *     a stream).  Between steps; synchronises the engine's streams.  DSM_ERR_INVALID, nothing changed, for a rate or format
+ *     outside the definition; DSM_ERR_STATE while ingest is off.  dsm_mimi_reset_slot clears the encoder side's history,
+ *     dsm_asr_reset_slot the model side's; the format stays across resets, as a bias attachment does.
+ *   dsm_asr_input_format      the slot's format, its frame in samples and bytes, and D; any pointer may be NULL.
+ *   dsm_mimi_encode_step_raw, _raw_async, _raw_dev, dsm_asr_step_raw  their plain siblings — same streams, events, ticket ring and
+ *     lock — with "upload 1920 floats per slot" replaced by "upload the raw rows, launch ingest_resample_kernel", which writes
+ *     the frames where the upload writes them.  raw: [B][pitch_bytes], slot b's frame in the first frame_bytes(b) bytes of its
+ *     row; pitch_bytes % 16 == 0, at most 15360, and at least every ACTIVE slot's frame_bytes (DSM_ERR_INVALID otherwise, no
+ *     state changed; the _dev variant, whose mask is on the device, checks against every slot).  A masked-off slot's row is not
+ *     read and its history stays.  d_raw must be 16-byte aligned.
+ *   dsm_debug_ingest_read     test aid: the frames [B][1920] the side's (0 encoder, 1 model) last raw call handed to Mimi.
+ *   dsm_ingest_host_*         host only, no device: one slot's streaming state going through the same header functions as the
+ *     kernel.  dsm_ingest_host takes one frame of the format's frame_bytes and writes 1920 samples.
+ *   dsm_ingest_describe       host only: the twelve words of a format's descriptor (rate, fmt, L, M, half, taps, F_in,
+ *     frame_bytes, D, 0, table words, 0), or DSM_ERR_INVALID with dsm_last_error(NULL) saying why.
+ *   dsm_ingest_g711_table     host only: the 256 expanded 16-bit values of DSM_PCM_MULAW / DSM_PCM_ALAW.
+ *   dsm_worker_set_input_rate  for an open channel of an engine-backed worker (DSM_ERR_STATE on a caller-supplied backend or
+ *     a closed channel, and once the channel's audio has been cut into frames; DSM_ERR_INVALID for a rate outside the
+ *     definition): the channel's InMsg::Audio samples are f32 at `hz`.  Turns ingest on if it is off.  The channel's queue is cut
+ *     into frames of F_in samples; Step.buffered_pcm counts the channel's own samples; a Marker counts queued frames in units of
+ *     F_in and is due ONE STEP LATER than on a 24 kHz channel, because the last D output samples in front of it land in the next
+ *     frame.  While any open channel has such a rate, dsm_worker_step and dsm_worker_step_encode call
+ *     dsm_mimi_encode_step_raw_async (every channel's frame in a row of the longest open frame); when none has, exactly what they
+ *     call without this section.  The rate returns to 24000 when the channel goes back to the free list and in
+ *     dsm_worker_destroy, where and as the bias detach.  Wire bytes are unchanged.  dsm_worker_send_body and the Opus callback
+ *     path stay as they are (24 kHz).
+ * Slot snapshots carry neither format nor history: after dsm_asr_import_slots / dsm_asr_move_slots the destination slot keeps
+ * ITS OWN; the caller sets the format after an import (which also clears the history).  Sample formats other than f32 are an
+ * engine-level feature, for hosts that own their sockets. */
+#define DSM_PCM_F32 0
+#define DSM_PCM_S16 1
+#define DSM_PCM_MULAW 2
+#define DSM_PCM_ALAW 3
+typedef struct dsm_ingest_host_state dsm_ingest_host_state;
+int dsm_asr_set_ingest(dsm_engine*, int on);
+int dsm_asr_set_input_format(dsm_engine*, int slot, int sample_rate_hz, int sample_format);
+int dsm_asr_input_format(dsm_engine*, int slot, int* rate, int* fmt, int* frame_samples, int* frame_bytes, int* latency_samples_24k);
+int dsm_mimi_encode_step_raw(dsm_engine*, const void* raw, size_t pitch_bytes, const uint8_t* mask, uint32_t* codes_out, int* produced);
+int dsm_mimi_encode_step_raw_async(dsm_engine*, const void* raw, size_t pitch_bytes, const uint8_t* mask, int* ticket);
+int dsm_mimi_encode_step_raw_dev(dsm_engine*, const void* d_raw, size_t pitch_bytes, const uint8_t* d_mask, uint32_t* d_codes_out);
+int dsm_asr_step_raw(dsm_engine*, const void* raw, size_t pitch_bytes, const uint8_t* mask, uint32_t* codes_out,
+                     uint32_t* text_tokens_out, float* vad_prs_out);
+int dsm_debug_ingest_read(dsm_engine*, int side, float* out /*[B][1920]*/);
+dsm_ingest_host_state* dsm_ingest_host_new(int sample_rate_hz, int sample_format);
+void dsm_ingest_host_free(dsm_ingest_host_state*);
+int dsm_ingest_host(dsm_ingest_host_state*, const void* raw_frame, float* out1920);
+int dsm_ingest_describe(int sample_rate_hz, int sample_format, uint32_t* words12);
+int dsm_ingest_g711_table(int sample_format, int16_t* out256);
+int dsm_worker_set_input_rate(dsm_worker*, int slot, int hz);
+
 #ifdef __cplusplus
 }
 #endif
