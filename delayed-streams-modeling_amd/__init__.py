@@ -167,9 +167,13 @@ ABI_SYMBOLS = [
     "dsm_mimi_encode_step_raw_async", "dsm_mimi_encode_step_raw_dev", "dsm_asr_step_raw", "dsm_debug_ingest_read",
     "dsm_ingest_host_new", "dsm_ingest_host_free", "dsm_ingest_host", "dsm_ingest_describe", "dsm_ingest_g711_table",
     "dsm_worker_set_input_rate",
+    "dsm_tts_set_egress", "dsm_tts_set_output_format", "dsm_tts_output_format", "dsm_tts_step_raw", "dsm_tts_recv_raw",
+    "dsm_tts_collect_raw", "dsm_tts_debug_egress", "dsm_egress_host_new", "dsm_egress_host_free", "dsm_egress_host",
+    "dsm_egress_describe", "dsm_egress_encode_sample",
 ]
-PCM_F32, PCM_S16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3  # DSM_PCM_*: the sample formats of the ingest section
+PCM_F32, PCM_S16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3  # DSM_PCM_*: the sample formats of the ingest and egress sections
 INGEST_MAX_FRAME_BYTES = 15360  # the largest raw frame (48 kHz f32) and the largest pitch of the raw calls
+EGRESS_MAX_FRAME_BYTES = 15360  # the same on the way out: the largest row and pitch of the TTS raw calls
 BIAS_MAX_TOKENS, BIAS_MAX_KEYWORD_TOKENS, BIAS_MAX_NODES, BIAS_MAX_SETS = 1024, 32, 65535, 256  # DSM_BIAS_MAX_*
 BIAS_DEAD = 0xFFFFFFFF  # DSM_BIAS_DEAD: the trie node of a slot inside a word that left the trie
 
@@ -446,6 +450,23 @@ def load_library(path=None):
     for name in ("dsm_asr_set_ingest", "dsm_asr_set_input_format", "dsm_asr_input_format", "dsm_mimi_encode_step_raw",
                  "dsm_mimi_encode_step_raw_async", "dsm_mimi_encode_step_raw_dev", "dsm_asr_step_raw", "dsm_debug_ingest_read",
                  "dsm_ingest_host", "dsm_ingest_describe", "dsm_ingest_g711_table", "dsm_worker_set_input_rate"):
+        getattr(lib, name).restype = C.c_int
+    lib.dsm_tts_set_egress.argtypes = [vp, C.c_int]
+    lib.dsm_tts_set_output_format.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.dsm_tts_output_format.argtypes = [vp, C.c_int] + [intp] * 5
+    lib.dsm_tts_step_raw.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dsm_tts_recv_raw.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.dsm_tts_collect_raw.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.dsm_tts_debug_egress.argtypes = [vp, vp, vp, vp, C.c_size_t]
+    lib.dsm_egress_host_new.argtypes = [C.c_int, C.c_int]
+    lib.dsm_egress_host_new.restype = C.c_void_p
+    lib.dsm_egress_host_free.argtypes = [vp]
+    lib.dsm_egress_host_free.restype = None
+    lib.dsm_egress_host.argtypes = [vp, vp, vp]
+    lib.dsm_egress_describe.argtypes = [C.c_int, C.c_int, u32p]
+    lib.dsm_egress_encode_sample.argtypes = [C.c_int, C.c_float, vp]
+    for name in ("dsm_tts_set_egress", "dsm_tts_set_output_format", "dsm_tts_output_format", "dsm_tts_step_raw", "dsm_tts_recv_raw",
+                 "dsm_tts_collect_raw", "dsm_tts_debug_egress", "dsm_egress_host", "dsm_egress_describe", "dsm_egress_encode_sample"):
         getattr(lib, name).restype = C.c_int
     if path is None:
         _lib = lib
@@ -1070,6 +1091,66 @@ class ingest_host:
             pass
 
 
+def egress_describe(rate, fmt):
+    """dsm_egress_describe: the descriptor of an output format (csrc/dsm_egress.h) as a dict — rate, fmt, L, M, half, taps,
+    F_out, frame_bytes, D (the latency in output samples), table_words.  DsmError with the reason for a rate or format outside
+    the definition."""
+    lib = load_library()
+    w = np.zeros(12, dtype=np.uint32)
+    rc = lib.dsm_egress_describe(int(rate), int(fmt), _ptr(w))
+    if rc != 0:
+        msg = lib.dsm_last_error(None)
+        raise DsmError(f"dsm_egress_describe failed ({rc}): {msg.decode() if msg else '?'}")
+    names = ("rate", "fmt", "L", "M", "half", "taps", "F_out", "frame_bytes", "D", "table_off", "table_words", "reserved")
+    return {k: int(v) for k, v in zip(names, w) if k not in ("table_off", "reserved")}
+
+
+def egress_encode_sample(fmt, v):
+    """dsm_egress_encode_sample: one sample through the shared encoder — the f32 bits (uint32), the s16 value, or the G.711 byte."""
+    out = np.zeros(4, dtype=np.uint8)
+    if load_library().dsm_egress_encode_sample(int(fmt), C.c_float(v), _ptr(out)) != 0:
+        raise DsmError("dsm_egress_encode_sample: the format is none of DSM_PCM_*")
+    if fmt == PCM_F32:
+        return int(out.view("<u4")[0])
+    return int(out[:2].view("<i2")[0]) if fmt == PCM_S16 else int(out[0])
+
+
+class egress_host:
+    """dsm_egress_host_*: one slot's streaming egress on the host — the function egress_resample_kernel is bit-identical to.
+    step(frame) takes one emitted frame of 1920 f32 samples at 24 kHz and returns the format's frame as frame_bytes uint8."""
+
+    def __init__(self, rate, fmt=PCM_F32):
+        self.lib = load_library()
+        self.info = egress_describe(rate, fmt)  # raises with the reason for an unsupported format
+        self.frame_samples, self.frame_bytes, self.latency = self.info["F_out"], self.info["frame_bytes"], self.info["D"]
+        self.h = self.lib.dsm_egress_host_new(int(rate), int(fmt))
+        if not self.h:
+            msg = self.lib.dsm_last_error(None)
+            raise DsmError(f"dsm_egress_host_new failed: {msg.decode() if msg else '?'}")
+
+    def step(self, frame):
+        frame = np.ascontiguousarray(frame, dtype=np.float32)
+        if frame.size != FRAME_SIZE:
+            raise DsmError(f"egress_host.step: a frame of {frame.size} samples, a step has {FRAME_SIZE}")
+        out = np.zeros(self.frame_bytes, dtype=np.uint8)
+        rc = self.lib.dsm_egress_host(self.h, _ptr(frame), _ptr(out))
+        if rc != 0:
+            msg = self.lib.dsm_last_error(None)
+            raise DsmError(f"dsm_egress_host failed ({rc}): {msg.decode() if msg else '?'}")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.dsm_egress_host_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LinearResampler:
     """kyutai-client-core `LinearResampler` (audio.rs:133-183) behind the C ABI; process() is streaming."""
 
@@ -1596,6 +1677,51 @@ class TtsEngine:
     def pcm_pending(self):
         return self._check(self.lib.dsm_tts_pcm_pending(self.h))
 
+    # egress (include/dsm.h "egress"): per-slot output sample rate and sample format, resampled and encoded on the device
+    def set_egress(self, on):
+        """dsm_tts_set_egress: the engine-wide switch; on allocates the section, and decodes then deliver raw rows only."""
+        self._check(self.lib.dsm_tts_set_egress(self.h, 1 if on else 0))
+
+    def set_output_format(self, slot, rate, fmt=PCM_F32):
+        """dsm_tts_set_output_format: the slot's format from its next emitted frame on; clears its history."""
+        self._check(self.lib.dsm_tts_set_output_format(self.h, int(slot), int(rate), int(fmt)))
+
+    def output_format(self, slot):
+        """(rate, fmt, frame_samples, frame_bytes, latency in output samples) of the slot."""
+        v = [C.c_int(0) for _ in range(5)]
+        self._check(self.lib.dsm_tts_output_format(self.h, int(slot), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def step_raw(self, prev_text_token, allowed, mask, defer=False, pitch=EGRESS_MAX_FRAME_BYTES, fill=0):
+        """step_pcm's raw sibling.  Returns (text, audio, rows [B][pitch] uint8, valid [B]): slot b's frame is the first
+        frame_bytes(b) bytes of its row, everything else keeps `fill`.  defer=True: (text, audio), rows through recv_raw()."""
+        prev = np.ascontiguousarray(prev_text_token, dtype=np.uint32).reshape(self.B)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32).reshape(self.B)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        text = np.zeros(self.B, dtype=np.uint32)
+        audio = np.zeros((self.B, self.S), dtype=np.uint32)
+        rows = None if defer else np.full((self.B, pitch), fill, dtype=np.uint8)
+        valid = None if defer else np.zeros(self.B, dtype=np.uint8)
+        self._check(self.lib.dsm_tts_step_raw(self.h, _ptr(prev), _ptr(allowed), _ptr(mask), _ptr(text), _ptr(audio),
+                                              _ptr(rows), pitch, _ptr(valid)))
+        return (text, audio) if defer else (text, audio, rows, valid)
+
+    def recv_raw(self, pitch=EGRESS_MAX_FRAME_BYTES, fill=0):
+        """The oldest deferred step's (rows [B][pitch], valid), or None when nothing is pending."""
+        rows = np.full((self.B, pitch), fill, dtype=np.uint8)
+        valid = np.zeros(self.B, dtype=np.uint8)
+        if self._check(self.lib.dsm_tts_recv_raw(self.h, _ptr(rows), pitch, _ptr(valid))) == 0:
+            return None
+        return rows, valid
+
+    def debug_egress(self, pcm, valid, pitch=EGRESS_MAX_FRAME_BYTES, fill=0):
+        """dsm_tts_debug_egress: the kernel alone on frames [B][1920] and valid flags [B]; rows [B][pitch] uint8."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(self.B, FRAME_SIZE)
+        valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(self.B)
+        rows = np.full((self.B, pitch), fill, dtype=np.uint8)
+        self._check(self.lib.dsm_tts_debug_egress(self.h, _ptr(pcm), _ptr(valid), _ptr(rows), pitch))
+        return rows
+
     def audio_tokens(self, slot, step):
         out = np.zeros(self.S, dtype=np.uint32)
         self._check(self.lib.dsm_tts_audio_tokens(self.h, slot, step, _ptr(out)))
@@ -1702,6 +1828,26 @@ class TtsEngine:
         k = blk.n_steps
         events = [(e.slot, e.word, e.start_step, e.stop_step) for e in ev[:blk.n_events]]
         return TtsBlock(k, stepped[:k], text[:k], audio[:k], None if pcm is None else pcm[:k],
+                        None if valid is None else valid[:k], events, status)
+
+    def collect_raw(self, pitch=EGRESS_MAX_FRAME_BYTES, fill=0):
+        """collect()'s raw sibling (egress on): the TtsBlock's pcm is the raw rows [n][B][pitch] uint8 — slot b's frame of step
+        s in the first frame_bytes(b) bytes of its row, everything else keeps `fill` (None unless run(decode=True))."""
+        n, decode = getattr(self, "_run", None) or (TTS_RUN_MAX, False)
+        B = self.B
+        stepped = np.zeros((n, B), dtype=np.uint8)
+        text = np.zeros((n, B), dtype=np.uint32)
+        audio = np.zeros((n, B, self.S), dtype=np.uint32)
+        rows = np.full((n, B, pitch), fill, dtype=np.uint8) if decode else None
+        valid = np.zeros((n, B), dtype=np.uint8) if decode else None
+        status = np.zeros(B, dtype=np.int32)
+        ev = (TtsWordEvent * (n * B))()
+        blk = TtsBlockC(0, _ptr(stepped), _ptr(text), _ptr(audio), None, _ptr(valid), ev, n * B, 0, _ptr(status))
+        self._check(self.lib.dsm_tts_collect_raw(self.h, C.byref(blk), _ptr(rows), pitch))
+        self._run = None
+        k = blk.n_steps
+        events = [(e.slot, e.word, e.start_step, e.stop_step) for e in ev[:blk.n_events]]
+        return TtsBlock(k, stepped[:k], text[:k], audio[:k], None if rows is None else rows[:k],
                         None if valid is None else valid[:k], events, status)
 
     def request_status(self, slot):

@@ -1166,6 +1166,7 @@ int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, 
 #include "dsm_tts_voice.inc"
 #include "dsm_tts_slot_state.inc"
 #include "dsm_tts_request.inc"
+#include "dsm_egress.inc"
 #include "dsm_speaker.inc"
 #include "dsm_tts_cond.inc"
 #include "dsm_audio.inc"

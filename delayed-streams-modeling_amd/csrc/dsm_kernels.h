@@ -19,6 +19,7 @@
 #include "dsm_token_scores.h"
 #include "dsm_text_bias.h"
 #include "dsm_ingest.h"
+#include "dsm_egress.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short dsm_bf16x8 __attribute__((ext_vector_type(8)));
@@ -3137,5 +3138,54 @@ __global__ __launch_bounds__(256) void ingest_resample_kernel(IngestArgs a) {
   const float* coef = a.coef + d.table_off;
   for (int n = tid; n < DSM_FRAME_SIZE; n += 256) out[n] = dsm_ingest_output(&d, coef, ingest_buf, started, n);
   for (uint32_t i = tid; i < d.taps; i += 256) hist[i] = ingest_buf[d.F_in + i];  // LDS is read-only since the barrier
+  if (tid == 0) a.started[b] = 1u;
+}
+
+// ------------------------------------------------------------------------------------------
+// Egress (dsm_egress.h; this project's own, off by default): the 1920 samples at 24 kHz a slot's decode produced — MimiDecState::pcm
+// — to a frame of the slot's own output sample rate and sample format, in the slot's row of the staging buffer the download
+// reads.  The ingest kernel run the other way, and the same shape: one 256-thread workgroup per slot; the slot's history and its
+// frame are staged in dynamic LDS as f32 (at most 204 + 1920 floats); each thread walks outputs n = tid, tid + 256, ... < F_out
+// with the serial fp64 chain of dsm_egress_output (v_fma_f64 gives the host's multiply-add bits), encodes and stores the sample
+// (a dword, a short or a byte: at most 3840 stores a row); then the frame's last `taps` samples become the history.  A slot that
+// does not emit returns at once: nothing read, nothing written.  Every index is bounded by the descriptor, which the engine
+// admits through dsm_egress::check only: LDS taps + 1920 <= 2124 floats, coefficient reads inside the table, stores inside
+// frame_bytes <= 15360 <= pitch.
+// ------------------------------------------------------------------------------------------
+struct EgressArgs {
+  const float* pcm;             // [B][DSM_FRAME_SIZE] the decoder's frames
+  const uint8_t* valid;         // [B] the decoder's mask: the slot emits
+  const uint32_t* slot_desc;    // [B] index into descs
+  const dsm_egress_desc* descs;
+  const float* coef;            // the coefficient arena
+  float* hist;                  // [B][DSM_EGRESS_MAX_TAPS]
+  uint32_t* started;            // [B]
+  uint8_t* raw;                 // [B][pitch] bytes, rows 16-byte aligned
+  size_t pitch;
+};
+
+constexpr size_t egress_lds() { return sizeof(float) * (DSM_EGRESS_MAX_TAPS + DSM_FRAME_SIZE); }
+__global__ __launch_bounds__(256) void egress_resample_kernel(EgressArgs a) {
+  extern __shared__ float egress_buf[];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (!a.valid[b]) return;
+  const dsm_egress_desc d = a.descs[a.slot_desc[b]];
+  const float* frame = a.pcm + (size_t)b * DSM_FRAME_SIZE;
+  uint8_t* row = (uint8_t*)__builtin_assume_aligned(a.raw + (size_t)b * a.pitch, 16);
+  if (d.taps == 0u && d.fmt == DSM_PCM_F32) {  // pass-through: the bits as they are, no state but "started"
+    const uint32_t* src = (const uint32_t*)frame;
+    uint32_t* dst = (uint32_t*)row;
+    for (int n = tid; n < DSM_FRAME_SIZE; n += 256) dst[n] = src[n];
+    if (tid == 0) a.started[b] = 1u;
+    return;
+  }
+  float* hist = a.hist + (size_t)b * DSM_EGRESS_MAX_TAPS;
+  const uint32_t started = a.started[b];
+  for (uint32_t i = tid; i < d.taps; i += 256) egress_buf[i] = started ? hist[i] : 0.0f;
+  for (uint32_t i = tid; i < DSM_FRAME_SIZE; i += 256) egress_buf[d.taps + i] = frame[i];
+  __syncthreads();
+  const float* coef = a.coef + d.table_off;
+  for (uint32_t n = tid; n < d.F_out; n += 256) dsm_egress_store(d.fmt, row, n, dsm_unpaired(dsm_egress_output(&d, coef, egress_buf, started, (int)n)));
+  for (uint32_t i = tid; i < d.taps; i += 256) hist[i] = egress_buf[DSM_FRAME_SIZE + i];  // LDS is read-only since the barrier
   if (tid == 0) a.started[b] = 1u;
 }

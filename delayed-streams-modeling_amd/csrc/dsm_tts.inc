@@ -138,6 +138,10 @@ struct dsm_tts : DsmDevice {
     float* h_pcm = nullptr;     // [B][DSM_FRAME_SIZE]
     uint8_t* h_valid = nullptr; // [B]
     bool launched = false;      // false: no slot could emit, nothing was enqueued, valid is all zero
+    // egress (dsm_egress.inc): with the section on the entry receives raw rows in the place of h_pcm
+    uint8_t* h_raw = nullptr;   // [B][DSM_EGRESS_MAX_FRAME_BYTES] pinned, allocated by the first dsm_tts_set_egress(1)
+    size_t raw_pitch = 0;       // the pitch the rows of this entry were written and downloaded at
+    std::vector<uint32_t> fb;   // [B] every slot's frame_bytes when the entry was enqueued
   };
   PcmEntry pcm_q[2];
   uint64_t pcm_seq = 0;  // step_pcm calls so far: entry / frame buffer of call n is n & 1
@@ -172,6 +176,21 @@ struct dsm_tts : DsmDevice {
   PcmEntry blk_pcm[DSM_TTS_RUN_MAX];
   int blk_pending = 0;    // steps of the block that waits for dsm_tts_collect (0: none)
   bool blk_decode = false;
+  // ---- egress (dsm_tts_set_egress; dsm_egress.h, dsm_egress.inc): a sample rate and a sample format per slot ----
+  // What egress_resample_kernel reads: the format descriptors [kEgressFormats] (entry 0 = 24000 / F32, append-only: one per
+  // (rate, format) ever set), the coefficient arena (append-only: one phase table per rate), each slot's descriptor index [B],
+  // the history [B][204] and the "started" words [B]; what it writes: the staging rows [B][15360], at egress_pitch — the largest
+  // frame_bytes of any slot, rounded up to 16 — which is also what a step downloads.  All of it allocated by the first
+  // dsm_tts_set_egress(1), with a pinned raw buffer beside every PcmEntry.  Host side: mirrors of the descriptors and indices.
+  static constexpr size_t kEgressFormats = 64, kEgressCoefWords = (size_t)1 << 20;
+  bool egress_on = false, egress_ready = false;
+  dsm_egress_desc* egress_descs_d = nullptr;
+  float *egress_coef_d = nullptr, *egress_hist = nullptr, *egress_dbg_pcm = nullptr;
+  uint32_t *egress_slot_desc_d = nullptr, *egress_started = nullptr;
+  uint8_t *egress_raw_d = nullptr, *egress_dbg_valid = nullptr;
+  std::vector<dsm_egress_desc> egress_descs_h;
+  std::vector<uint32_t> egress_slot_desc_h;
+  size_t egress_coef_used = 0, egress_pitch = sizeof(float) * DSM_FRAME_SIZE;
 };
 
 namespace {
@@ -625,6 +644,8 @@ int tts_group_body(dsm_tts* t, hipStream_t st, dsm_tts::Grp& grp, bool run_dep) 
   return 0;
 }
 
+int egress_enqueue(dsm_tts* t, hipStream_t sd, dsm_tts::PcmEntry& en);  // dsm_egress.inc
+
 // Mimi::decode_step of the frames buffer `sel` holds, on the decode stream behind the step's groups; PCM and valid flags go
 // to the entry's pinned buffers, its event closes the sequence.
 int tts_enqueue_decode(dsm_tts* t, int sel, dsm_tts::PcmEntry& en) {
@@ -637,7 +658,11 @@ int tts_enqueue_decode(dsm_tts* t, int sel, dsm_tts::PcmEntry& en) {
   HIPCHK(hipMemcpyAsync(d.codes, t->d_fcodes + (size_t)sel * B * S, sizeof(uint32_t) * (size_t)B * S, hipMemcpyDeviceToDevice, sd));
   HIPCHK(hipMemcpyAsync(d.mask, t->d_fvalid + (size_t)sel * B, (size_t)B, hipMemcpyDeviceToDevice, sd));
   if (int rc = mimi_decode(e, t->mimi_w, d, B, sd)) return rc;
-  HIPCHK(hipMemcpyAsync(en.h_pcm, d.pcm, sizeof(float) * (size_t)B * DSM_FRAME_SIZE, hipMemcpyDeviceToHost, sd));
+  if (t->egress_on) {  // the raw rows in the place of the f32 frames
+    if (int rc = egress_enqueue(t, sd, en)) return rc;
+  } else {
+    HIPCHK(hipMemcpyAsync(en.h_pcm, d.pcm, sizeof(float) * (size_t)B * DSM_FRAME_SIZE, hipMemcpyDeviceToHost, sd));
+  }
   HIPCHK(hipMemcpyAsync(en.h_valid, d.mask, (size_t)B, hipMemcpyDeviceToHost, sd));
   HIPCHK(hipEventRecord(en.ev, sd));
   en.launched = true;
@@ -864,6 +889,7 @@ int dsm_tts_step_pcm(dsm_tts* t, const uint32_t* prev_text_token, const int32_t*
   if (!t || !prev_text_token || !allowed || !mask) return DSM_ERR_INVALID;
   DsmDevice* e = t;
   if (!t->mimi) { e->set_error("dsm_tts_step_pcm needs dsm_tts_attach_mimi first"); return DSM_ERR_STATE; }
+  if (t->egress_on) { e->set_error("egress is on: dsm_tts_step_raw delivers the frames"); return DSM_ERR_STATE; }
   if (pcm_out && t->pcm_pending > 0) {
     e->set_error("%d deferred step(s) wait for dsm_tts_recv_pcm: a serial step would deliver out of order", t->pcm_pending);
     return DSM_ERR_STATE;
@@ -880,6 +906,7 @@ int dsm_tts_step_pcm(dsm_tts* t, const uint32_t* prev_text_token, const int32_t*
 
 int dsm_tts_recv_pcm(dsm_tts* t, float* pcm_out, uint8_t* pcm_valid_out) {
   if (!t) return DSM_ERR_INVALID;
+  if (t->egress_on) { t->set_error("egress is on: dsm_tts_recv_raw delivers the frames"); return DSM_ERR_STATE; }
   if (t->pcm_pending == 0) return 0;
   DsmDevice* e = t;
   HIPCHK(hipSetDevice(e->device));
@@ -1098,7 +1125,8 @@ int dsm_tts_reset_slot(dsm_tts* t, int slot) {
   if (t->mimi) {
     // The slot's next generation decodes with a fresh Mimi (srv/tts.rs:499-500: clone() + reset_state()): conv states and carries
     // zero, not started, and — unlike Mimi::reset_batch_idx — the decoder transformer back at position 0.  On the decode stream,
-    // i.e. behind the decodes already queued for the old generation.
+    // i.e. behind the decodes already queued for the old generation.  Egress: the slot's history goes with it, its format stays.
+    if (t->egress_ready) HIPCHK(hipMemsetAsync(t->egress_started + slot, 0, sizeof(uint32_t), e->s_enc));
     return reset_decoder_slot(e, t->mimi_w, t->dec, e->s_enc, slot, true);
   }
   return 0;

@@ -105,7 +105,8 @@ int tts_run_impl(dsm_tts* t, int n_steps, bool decode) {
   return 0;
 }
 
-int tts_collect_impl(dsm_tts* t, dsm_tts_block* out) {
+// raw (dsm_tts_collect_raw, egress on): [n][B][pitch] rows in the place of out->pcm, which is NULL then
+int tts_collect_impl(dsm_tts* t, dsm_tts_block* out, uint8_t* raw = nullptr, size_t pitch = 0) {
   DsmDevice* e = t;
   const dsm_tts_config& c = t->cfg;
   const int B = t->B, S = c.dep_num_slices, n = t->blk_pending, ld = t->rec_ld;
@@ -116,6 +117,15 @@ int tts_collect_impl(dsm_tts* t, dsm_tts_block* out) {
   if (t->blk_decode)
     for (int s = 0; s < n; ++s)
       if (t->blk_pcm[s].launched) HIPCHK(hipEventSynchronize(t->blk_pcm[s].ev));
+  if (raw && t->blk_decode)  // a pitch below an emitted frame is refused before anything is consumed
+    for (int s = 0; s < n; ++s) {
+      const dsm_tts::PcmEntry& en = t->blk_pcm[s];
+      for (int b = 0; en.launched && b < B; ++b)
+        if (en.h_valid[b] && en.fb[(size_t)b] > pitch) {
+          e->set_error("raw frames: slot %d's frame has %u bytes, the pitch is %zu", b, en.fb[(size_t)b], pitch);
+          return DSM_ERR_INVALID;
+        }
+    }
   out->n_steps = n;
   out->n_events = 0;
   for (int s = 0; s < n; ++s)
@@ -129,10 +139,11 @@ int tts_collect_impl(dsm_tts* t, dsm_tts_block* out) {
       if (out->text_token) out->text_token[at_sb] = stepped ? text_token : 0;
       if (out->audio)
         for (int k = 0; k < S; ++k) out->audio[at_sb * S + k] = (uint32_t)rec[TTS_REC_HDR + k];
-      if (out->pcm_valid || out->pcm) {
+      if (out->pcm_valid || out->pcm || raw) {
         const dsm_tts::PcmEntry& en = t->blk_pcm[s];
         const bool v = t->blk_decode && en.launched && en.h_valid[b];
         if (out->pcm_valid) out->pcm_valid[at_sb] = v ? 1 : 0;
+        if (raw && v) memcpy(raw + at_sb * pitch, en.h_raw + (size_t)b * en.raw_pitch, en.fb[(size_t)b]);
         if (out->pcm && v)
           memcpy(out->pcm + at_sb * DSM_FRAME_SIZE, en.h_pcm + (size_t)b * DSM_FRAME_SIZE, sizeof(float) * DSM_FRAME_SIZE);
       }
@@ -323,6 +334,7 @@ int dsm_tts_run(dsm_tts* t, int n_steps, int decode) {
 int dsm_tts_collect(dsm_tts* t, dsm_tts_block* out) {
   if (!t || !out) return DSM_ERR_INVALID;
   if (!t->blk_pending) { t->set_error("no block waits: dsm_tts_run first"); return DSM_ERR_STATE; }
+  if (t->egress_on && t->blk_decode && out->pcm) { t->set_error("egress is on: dsm_tts_collect_raw delivers the frames"); return DSM_ERR_STATE; }
   return tts_collect_impl(t, out);
 }
 

@@ -1027,6 +1027,62 @@ int dsm_ingest_describe(int sample_rate_hz, int sample_format, uint32_t* words12
 int dsm_ingest_g711_table(int sample_format, int16_t* out256);
 int dsm_worker_set_input_rate(dsm_worker*, int slot, int hz);
 
+/* ---- egress: per-slot TTS output sample rate and sample format, resampled and encoded on the device (this project's own: the
+ * reference's TTS sockets send 24 kHz f32, srv/tts.rs:528-544).  The ingest section run the other way — the same rates, the same
+ * DSM_PCM_* formats, the same filter family.  Off by default: nothing is allocated and every other call enqueues exactly what it
+ * enqueues without this section.  Definition (csrc/dsm_egress.h, bit-identical on host and device): a slot's FORMAT is a sample
+ * rate — 8000 .. 48000 Hz with a whole number F_out = 2 rate / 25 of samples per 80 ms frame — and a sample format:
+ * DSM_PCM_F32, DSM_PCM_S16 (little endian, rint(v 32768) clamped, NaN 0), DSM_PCM_MULAW, DSM_PCM_ALAW (ITU-T G.711 of that
+ * 16-bit value).  With x the slot's emitted PCM since the format was set (only the frames whose valid flag is 1) and
+ * y = dsm_resample(x, 24000, rate), the slot's e-th emitted frame is z_e[n] = y[F_out e + n - D], 0 in front of the stream:
+ * D = floor(half L / M) output samples (34 at 8 kHz, 33 at 11.025 kHz, 34 at 16 kHz, 33 at 22.05 kHz, 45 at 32 kHz, 62 at
+ * 44.1 kHz, 68 at 48 kHz; 0 at 24 kHz) is the format's latency.  The last D output samples of a generation (at most 4.25 ms)
+ * are never delivered; there is no flush.  24000 / F32 is the pass-through format and every slot's default: the step's 1920
+ * floats bit for bit.
+ *   dsm_tts_set_egress        engine-wide switch; needs an attached Mimi, no deferred step waiting and no block waiting
+ *     (DSM_ERR_STATE otherwise, nothing changed).  On: allocates the section (per-slot format and history, the coefficient
+ *     arena, a device staging of 15360 bytes a slot, a pinned raw buffer beside every queue entry), lets the raw calls run, and
+ *     every decode then downloads the raw rows IN THE PLACE of the 1920 floats; dsm_tts_step_pcm, dsm_tts_recv_pcm and
+ *     dsm_tts_collect with out->pcm on a decode block return DSM_ERR_STATE with nothing touched.  Off: the raw calls return
+ *     DSM_ERR_STATE.  Formats and histories stay across off / on.
+ *   dsm_tts_set_output_format sets the slot's format and clears its history (the next emitted frame is the first of a stream).
+ *     Between steps; synchronises the engine's streams.  DSM_ERR_INVALID, nothing changed, for a rate or format outside the
+ *     definition; DSM_ERR_STATE while egress is off or a block waits.  dsm_tts_reset_slot clears the history and keeps the
+ *     format; frames queued before a reset are still delivered.
+ *   dsm_tts_output_format     the slot's format, its frame in samples and bytes, and D; any pointer may be NULL.
+ *   dsm_tts_step_raw, dsm_tts_recv_raw, dsm_tts_collect_raw  their plain siblings dsm_tts_step_pcm, dsm_tts_recv_pcm and
+ *     dsm_tts_collect — same streams, events, queue of two, lock, emit rule and refusals.  raw: [B][pitch_bytes] (collect:
+ *     [n][B][pitch_bytes]); slot b's frame is the first frame_bytes(b) bytes of its row, the rest of the row and the row of a
+ *     slot that did not emit are not written.  pitch_bytes % 16 == 0, at most 15360, and at least every active slot's
+ *     frame_bytes (DSM_ERR_INVALID otherwise, no state changed; recv and collect check the slots that emitted, and the entry
+ *     or block stays queued).  dsm_tts_step_raw with raw_out NULL defers, as dsm_tts_step_pcm with pcm_out NULL
+ *     (pitch_bytes is not read then).
+ *     dsm_tts_collect_raw fills `out` exactly as dsm_tts_collect does, and out->pcm must be NULL.
+ *   dsm_tts_debug_egress      test aid: with egress on and nothing queued, runs egress_resample_kernel once on the caller's
+ *     frames [B][1920] and valid flags [B] through the slots' current formats and histories (which advance) and returns the rows.
+ *   dsm_egress_host_*         host only, no device: one slot's streaming state going through the same header functions as the
+ *     kernel.  dsm_egress_host takes one emitted frame of 1920 samples and writes the format's frame_bytes.
+ *   dsm_egress_describe       host only: the twelve words of a format's descriptor (rate, fmt, L, M, half, taps, F_out,
+ *     frame_bytes, D, 0, table words, 0), or DSM_ERR_INVALID with dsm_last_error(NULL) saying why.
+ *   dsm_egress_encode_sample  host only: one sample through the shared encoder; writes 4, 2, 1 or 1 bytes.
+ * Slot snapshots carry neither format nor history: after dsm_tts_import_slots, a move or a fork, the destination slot keeps
+ * ITS OWN; the caller sets the format after an import (which also clears the history). */
+typedef struct dsm_egress_host_state dsm_egress_host_state;
+int dsm_tts_set_egress(dsm_tts*, int on);
+int dsm_tts_set_output_format(dsm_tts*, int slot, int sample_rate_hz, int sample_format);
+int dsm_tts_output_format(dsm_tts*, int slot, int* rate, int* fmt, int* frame_samples, int* frame_bytes, int* latency_samples);
+int dsm_tts_step_raw(dsm_tts*, const uint32_t* prev_text_token, const int32_t* allowed, const uint8_t* mask,
+                     uint32_t* text_token_out, uint32_t* audio_out, void* raw_out /* [B][pitch_bytes] or NULL = deferred */,
+                     size_t pitch_bytes, uint8_t* valid_out);
+int dsm_tts_recv_raw(dsm_tts*, void* raw_out, size_t pitch_bytes, uint8_t* valid_out);
+int dsm_tts_collect_raw(dsm_tts*, dsm_tts_block* out, void* raw /* [n][B][pitch_bytes] */, size_t pitch_bytes);
+int dsm_tts_debug_egress(dsm_tts*, const float* pcm /*[B][1920]*/, const uint8_t* valid /*[B]*/, void* raw_out, size_t pitch_bytes);
+dsm_egress_host_state* dsm_egress_host_new(int sample_rate_hz, int sample_format);
+void dsm_egress_host_free(dsm_egress_host_state*);
+int dsm_egress_host(dsm_egress_host_state*, const float* frame1920, void* raw_out);
+int dsm_egress_describe(int sample_rate_hz, int sample_format, uint32_t* words12);
+int dsm_egress_encode_sample(int sample_format, float v, void* out);
+
 #ifdef __cplusplus
 }
 #endif
