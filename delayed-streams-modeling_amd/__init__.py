@@ -133,7 +133,7 @@ ABI_SYMBOLS = [
     "dsm_asr_create", "dsm_asr_create_from_arena", "dsm_asr_weight_arena", "dsm_destroy", "dsm_last_error", "dsm_mimi_encode_step", "dsm_asr_step_tokens",
     "dsm_asr_step_pcm", "dsm_asr_poll_msgs", "dsm_asr_reset_slot", "dsm_mimi_reset_slot", "dsm_sync",
     "dsm_get_metrics", "dsm_batch_size", "dsm_n_q", "dsm_mimi_encode_step_dev", "dsm_asr_step_tokens_dev",
-    "dsm_streams_join", "dsm_debug_read", "dsm_debug_gemm_plan", "dsm_asr_step_pcm_dev", "dsm_prof_enable", "dsm_prof_read",
+    "dsm_streams_join", "dsm_debug_read", "dsm_debug_gemm_plan", "dsm_debug_gemm_plan_knobs", "dsm_debug_gemm", "dsm_asr_step_pcm_dev", "dsm_prof_enable", "dsm_prof_read",
     "dsm_asr_export_slots", "dsm_asr_import_slots", "dsm_asr_move_slots", "dsm_slot_blob_info",
     "dsm_asr_create_replica", "dsm_asr_set_seed", "dsm_debug_set_positions", "dsm_debug_set_text_tokens", "dsm_mimi_decode_step", "dsm_mimi_decode_step_dev",
     "dsm_lm_stream_groups", "dsm_debug_serialize_groups", "dsm_prof_read_device", "dsm_prof_timeline", "dsm_prof_timeline_read",
@@ -176,6 +176,28 @@ INGEST_MAX_FRAME_BYTES = 15360  # the largest raw frame (48 kHz f32) and the lar
 EGRESS_MAX_FRAME_BYTES = 15360  # the same on the way out: the largest row and pitch of the TTS raw calls
 BIAS_MAX_TOKENS, BIAS_MAX_KEYWORD_TOKENS, BIAS_MAX_NODES, BIAS_MAX_SETS = 1024, 32, 65535, 256  # DSM_BIAS_MAX_*
 BIAS_DEAD = 0xFFFFFFFF  # DSM_BIAS_DEAD: the trie node of a slot inside a word that left the trie
+
+
+class DebugRowMap(C.Structure):
+    """dsm_debug_rowmap (include/dsm.h): row r starts at element (r // rpb) * bstride + (r % rpb + toff) * ld."""
+    _fields_ = [("bstride", C.c_int64), ("rpb", C.c_int32), ("ld", C.c_int32), ("toff", C.c_int32), ("pad_", C.c_int32)]
+
+
+class DebugGemmArgs(C.Structure):
+    """dsm_debug_gemm_args (include/dsm.h)."""
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("weight_bf16", C.c_int32), ("epi", C.c_int32), ("act", C.c_int32), ("may_defer", C.c_int32), ("norm_rms", C.c_int32),
+                ("knobs", C.c_int32 * 5), ("w_changed", C.c_int32),
+                ("X", C.c_void_p), ("x_len", C.c_uint64), ("xmap", DebugRowMap),
+                ("W", C.c_void_p), ("bias", C.c_void_p), ("scale", C.c_void_p),
+                ("res", C.c_void_p), ("res_len", C.c_uint64), ("rmap", DebugRowMap),
+                ("Y", C.c_void_p), ("y_len", C.c_uint64), ("ymap", DebugRowMap),
+                ("Y2", C.c_void_p), ("y2_len", C.c_uint64), ("y2map", DebugRowMap),
+                ("norm_w", C.c_void_p), ("norm_b", C.c_void_p), ("norm_out", C.c_void_p), ("norm_len", C.c_uint64),
+                ("x_back", C.c_void_p), ("res_back", C.c_void_p)]
+
+
+EPI_STORE, EPI_QKV, EPI_GATE, EPI_RVQ = 0, 1, 2, 3  # the GEMM epilogues (dsm_debug_gemm_plan, dsm_debug_gemm)
 
 
 class BiasToken(C.Structure):
@@ -293,6 +315,10 @@ def load_library(path=None):
     lib.dsm_debug_serialize_groups.restype = C.c_int
     lib.dsm_debug_gemm_plan.argtypes = [C.c_int] * 9 + [C.c_char_p, C.c_size_t]
     lib.dsm_debug_gemm_plan.restype = C.c_int
+    lib.dsm_debug_gemm_plan_knobs.argtypes = [C.c_int, C.POINTER(C.c_int)] + [C.c_int] * 7 + [C.c_char_p, C.c_size_t]
+    lib.dsm_debug_gemm_plan_knobs.restype = C.c_int
+    lib.dsm_debug_gemm.argtypes = [vp, C.POINTER(DebugGemmArgs), C.c_char_p, C.c_size_t]
+    lib.dsm_debug_gemm.restype = C.c_int
     lib.dsm_wav_decode.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t),
                                    C.POINTER(C.c_int)]
     lib.dsm_wav_decode.restype = C.c_int
@@ -1567,6 +1593,40 @@ class AsrEngine:
         t = np.ascontiguousarray(tokens, dtype=np.uint32)
         assert t.shape == (self.B,)
         self._check(self.lib.dsm_debug_set_text_tokens(self.h, t.ctypes.data))
+
+    def debug_gemm(self, M, N, K, X, xmap, W, bf16, epi=EPI_STORE, bias=None, scale=None, act=0, res=None, rmap=None,
+                   Y=None, ymap=None, Y2=None, y2map=None, norm_w=None, norm_b=None, norm_out=None, may_defer=False,
+                   knobs=(-1, -1, -1, -1, -1)):
+        """dsm_debug_gemm, a test aid: one product through the engine's GEMM launcher.  X, res, Y, Y2 and norm_out are flat
+        float32 buffers, each with its row map (bstride, rpb, ld, toff); Y, Y2 and norm_out hold what the caller wants to find
+        again outside the M x N result.  W is [N][K] ([2 N][K] for the gate).  norm_b None with norm_w: RmsNorm.  Returns a dict:
+        plan (the line of the plan that ran), Y / Y2 / norm_out (the whole buffers afterwards, copies), x_back / res_back (the
+        device copies of X / res afterwards) and w_changed."""
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1)  # noqa: E731
+        X, W, bias, scale, res, norm_w, norm_b = (f32(a) for a in (X, W, bias, scale, res, norm_w, norm_b))
+        out = {k: (None if a is None else f32(a).copy()) for k, a in (("Y", Y), ("Y2", Y2), ("norm_out", norm_out))}
+        assert W.size == (2 * N if epi == EPI_GATE else N) * K, "W is [N][K] (the gate: [2 N][K])"
+        for name, a in (("bias", bias), ("scale", scale), ("norm_w", norm_w), ("norm_b", norm_b)):
+            assert a is None or a.size == N, name + " is [N]"
+        g = DebugGemmArgs()
+        g.M, g.N, g.K, g.weight_bf16, g.epi, g.act, g.may_defer = M, N, K, int(bool(bf16)), epi, act, int(bool(may_defer))
+        g.norm_rms = int(norm_w is not None and norm_b is None)
+        g.knobs = (C.c_int32 * 5)(*knobs)
+        back = {"x_back": np.zeros_like(X), "res_back": None if res is None else np.zeros_like(res)}
+        g.X, g.x_len, g.xmap, g.W = X.ctypes.data, X.size, DebugRowMap(*xmap), W.ctypes.data
+        g.bias, g.scale = _ptr(bias), _ptr(scale)
+        if res is not None:
+            g.res, g.res_len, g.rmap, g.res_back = res.ctypes.data, res.size, DebugRowMap(*rmap), back["res_back"].ctypes.data
+        if out["Y"] is not None:
+            g.Y, g.y_len, g.ymap = out["Y"].ctypes.data, out["Y"].size, DebugRowMap(*ymap)
+        if out["Y2"] is not None:
+            g.Y2, g.y2_len, g.y2map = out["Y2"].ctypes.data, out["Y2"].size, DebugRowMap(*y2map)
+        if out["norm_out"] is not None:
+            g.norm_w, g.norm_b, g.norm_out, g.norm_len = _ptr(norm_w), _ptr(norm_b), out["norm_out"].ctypes.data, out["norm_out"].size
+        g.x_back = back["x_back"].ctypes.data
+        plan = C.create_string_buffer(512)
+        self._check(self.lib.dsm_debug_gemm(self.h, C.byref(g), plan, len(plan)))
+        return dict(out, plan=plan.value.decode(), w_changed=bool(g.w_changed), **back)
 
     def prof_read_device(self):
         """Like prof_read, from the in-kernel device-clock brackets (attention classes only)."""

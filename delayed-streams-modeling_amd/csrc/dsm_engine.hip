@@ -934,15 +934,14 @@ void launch_form(const GemmPlan& p, hipStream_t st, const GemmArgs& a) {
 // (dsm_gemm_plan.h) and executes the plan — the workspace, the main launch, the reduce, the row norm.  It decides nothing itself
 // and does not write the caller's arguments.  slabs: non-null when the caller's next kernel can sum split-K slabs itself; its ws
 // is non-null on return exactly when they were left to it.
-template <typename WT, typename KVT, int EPI, int NT>
-int launch_gemm(DsmDevice* e, hipStream_t st, const GemmArgs& args, bool aligned, Slabs* slabs = nullptr) {
-  static_assert(EPI_STORE == GEMM_EPI_STORE && EPI_QKV == GEMM_EPI_QKV && EPI_GATE == GEMM_EPI_GATE && EPI_RVQ == GEMM_EPI_RVQ, "");
-  static_assert(LoopDepth<uint16_t, 1>::MAX == 4 && LoopDepth<uint16_t, 2>::MAX == 2 && LoopDepth<float, 1>::MAX == 2, "plan_gemm's `deep`");
+// What plan_gemm is asked for a launch's arguments, and the knobs of the device context it is asked with: launch_gemm's own
+// question, also put by dsm_debug_gemm before it launches (which epilogue a plan ends in decides what that aid can offer).
+GemmQuery gemm_query(const GemmArgs& args, bool weight_bf16, int epi, int nt, bool aligned, bool may_defer) {
   auto ok4 = [](const RowMap& m) { return m.ld % 4 == 0 && m.bstride % 4 == 0; };
   GemmQuery q;
-  q.weight_bf16 = sizeof(WT) == 2;
-  q.epi = EPI;
-  q.NT = NT;
+  q.weight_bf16 = weight_bf16;
+  q.epi = epi;
+  q.NT = nt;
   q.M = args.M; q.N = args.N; q.K = args.K; q.Kpad = args.Kpad;
   q.nt_stride = args.nt_stride;
   q.aligned = aligned;
@@ -950,14 +949,24 @@ int launch_gemm(DsmDevice* e, hipStream_t st, const GemmArgs& args, bool aligned
   q.has_bias = args.bias != nullptr; q.has_norm = args.norm_out != nullptr;
   q.y_ok4 = ok4(args.ymap); q.y2_ok4 = ok4(args.y2map); q.res_ok4 = ok4(args.rmap);
   q.y_bstride0 = args.ymap.bstride == 0;
-  q.may_defer = slabs != nullptr;
+  q.may_defer = may_defer;
+  return q;
+}
+GemmKnobs gemm_knobs(const DsmDevice* e) {
   GemmKnobs k;
   k.dot_mode = e->dot_mode;
   k.chunk_loop_min_tiles = e->chunk_loop_min_tiles;
   k.smallk_min_tiles = e->smallk_min_tiles;
   k.smallk_mt = e->smallk_mt;
   k.loop_depth = e->loop_depth;
-  const GemmPlan p = plan_gemm(q, k);
+  return k;
+}
+
+template <typename WT, typename KVT, int EPI, int NT>
+int launch_gemm(DsmDevice* e, hipStream_t st, const GemmArgs& args, bool aligned, Slabs* slabs = nullptr) {
+  static_assert(EPI_STORE == GEMM_EPI_STORE && EPI_QKV == GEMM_EPI_QKV && EPI_GATE == GEMM_EPI_GATE && EPI_RVQ == GEMM_EPI_RVQ, "");
+  static_assert(LoopDepth<uint16_t, 1>::MAX == 4 && LoopDepth<uint16_t, 2>::MAX == 2 && LoopDepth<float, 1>::MAX == 2, "plan_gemm's `deep`");
+  const GemmPlan p = plan_gemm(gemm_query(args, sizeof(WT) == 2, EPI, NT, aligned, slabs != nullptr), gemm_knobs(e));
   if (p.form == GEMM_NO_FIT) {
     e->set_error("GEMM K=%d: chunk partials do not fit in LDS", args.K);
     return DSM_ERR_INVALID;
@@ -1009,8 +1018,9 @@ int launch_gemm(DsmDevice* e, hipStream_t st, const GemmArgs& args, bool aligned
   e->prof_end(ph, st);
   HIPCHK(hipGetLastError());
   if (p.row_norm) {
-    hipLaunchKernelGGL(row_norm_kernel, dim3(a.M), dim3(256), 0, st, a.norm_out, a.Y, a.norm_w, a.norm_b, a.M,
-                       a.N, a.norm_eps, a.norm_rms);
+    // (a row wider than row_norm_kernel's registers hold: the two-pass form, same arithmetic)
+    hipLaunchKernelGGL(a.N > 1024 * DSM_ROW_ITS ? row_norm_wide_kernel : row_norm_kernel, dim3(a.M), dim3(256), 0, st, a.norm_out, a.Y,
+                       a.norm_w, a.norm_b, a.M, a.N, a.norm_eps, a.norm_rms);
     HIPCHK(hipGetLastError());
   }
   if (slabs) {

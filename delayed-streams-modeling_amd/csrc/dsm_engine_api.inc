@@ -1740,7 +1740,70 @@ int dsm_debug_read(dsm_engine* e, const char* name, float* out, size_t cap) {
 }
 
 int dsm_debug_gemm_plan(int stt, int dot_mode, int weight_bf16, int epi, int nt, int M, int N, int K, int flags, char* buf, size_t cap) {
-  if (epi < EPI_STORE || epi > EPI_RVQ || (nt != 1 && nt != 2) || M < 1 || N < 1 || K < 1 || !buf || !cap) return DSM_ERR_INVALID;
+  const int knobs[5] = {dot_mode, -1, -1, -1, -1};  // the kind's own knobs in this mode: one query path for both entry points
+  return dsm_debug_gemm_plan_knobs(stt, knobs, weight_bf16, epi, nt, M, N, K, flags, buf, cap);
+}
+
+}  // extern "C"
+
+namespace {
+// knobs[5] of the debug entry points over `base`: -1 keeps base's value; false when a value is none a DSM_* variable could set
+bool debug_knobs(const int* knobs, GemmKnobs* k) {
+  if (knobs[0] >= 0) k->dot_mode = knobs[0];
+  if (knobs[1] >= 0) k->chunk_loop_min_tiles = knobs[1];
+  if (knobs[2] >= 0) k->smallk_min_tiles = knobs[2];
+  if (knobs[3] >= 0) k->smallk_mt = knobs[3];
+  if (knobs[4] >= 0) k->loop_depth = knobs[4];
+  return (k->dot_mode == 0 || k->dot_mode == 1) && (k->smallk_mt == 1 || k->smallk_mt == 2 || k->smallk_mt == 4) &&
+         (k->loop_depth == 2 || k->loop_depth == 4);
+}
+
+// What a consumer of split-K slabs does (AttnFused, LogitSrc), as a plain store: Y[m][n..n+3] = the ordered slab sum.
+__global__ __launch_bounds__(256) void debug_slab_sum_kernel(float* Y, RowMap ymap, Slabs s, int M, int N) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const int n4 = N >> 2;
+  if (i >= (long)M * n4) return;
+  const int m = (int)(i / n4), n = (int)(i % n4) * 4;
+  const f32x4 v = slab_sum(s.ws + (long)m * s.ld + n, s.cstride, s.chunks);
+  float* y = Y + ymap.off(m) + n;
+  y[0] = v[0]; y[1] = v[1]; y[2] = v[2]; y[3] = v[3];
+}
+
+// A host buffer on the device for the length of one dsm_debug_gemm call (plain allocation, handed back by the destructor).
+struct DebugBuf {
+  DsmDevice* e;
+  float* d = nullptr;
+  explicit DebugBuf(DsmDevice* e_) : e(e_) {}
+  ~DebugBuf() { e->dfree(d); }
+  int put(const float* host, size_t n) {
+    if (int rc = e->dalloc(&d, n, false)) return rc;
+    HIPCHK(hipMemcpy(d, host, sizeof(float) * n, hipMemcpyHostToDevice));
+    return 0;
+  }
+};
+
+// one past the last element rows 0 .. M - 1 of `width` floats reach under a row map; 0 when the map is not one the aid takes
+size_t debug_extent(const dsm_debug_rowmap& m, int M, int width) {
+  if (m.bstride < 0 || m.rpb < 1 || m.ld < 0 || m.toff < 0) return 0;
+  const RowMap r{(long)m.bstride, m.rpb, m.ld, m.toff};
+  long hi = 0;
+  for (int i = 0; i < M; ++i) hi = std::max(hi, r.off(i) + width);
+  return (size_t)hi;
+}
+// output rows must not overlap each other (two workgroups would race for the shared elements)
+bool debug_rows_disjoint(const dsm_debug_rowmap& m, int M, int N) {
+  if (m.ld < N) return false;
+  return m.bstride == 0 ? m.rpb >= M : m.bstride >= (int64_t)(m.rpb + m.toff) * m.ld;
+}
+RowMap debug_map(const dsm_debug_rowmap& m) { return RowMap{(long)m.bstride, m.rpb, m.ld, m.toff}; }
+}  // namespace
+
+extern "C" {
+
+int dsm_debug_gemm_plan_knobs(int stt, const int* knobs, int weight_bf16, int epi, int nt, int M, int N, int K, int flags, char* buf, size_t cap) {
+  if (!knobs || epi < EPI_STORE || epi > EPI_RVQ || (nt != 1 && nt != 2) || M < 1 || N < 1 || K < 1 || !buf || !cap) return DSM_ERR_INVALID;
+  GemmKnobs k = gemm_default_knobs(stt != 0, knobs[0] < 0 ? 0 : knobs[0]);  // the defaults of the kind and mode, then the explicit entries
+  if (!debug_knobs(knobs, &k)) return DSM_ERR_INVALID;
   GemmQuery q;
   q.weight_bf16 = weight_bf16 != 0;
   q.epi = epi;
@@ -1754,7 +1817,133 @@ int dsm_debug_gemm_plan(int stt, int dot_mode, int weight_bf16, int epi, int nt,
   q.y_ok4 = flags & DSM_GEMMQ_Y_OK4; q.y2_ok4 = flags & DSM_GEMMQ_Y2_OK4; q.res_ok4 = flags & DSM_GEMMQ_RES_OK4;
   q.y_bstride0 = flags & DSM_GEMMQ_Y_PLAIN;
   q.may_defer = flags & DSM_GEMMQ_MAY_DEFER;
-  return gemm_plan_line(plan_gemm(q, gemm_default_knobs(stt != 0, dot_mode)), q.has_norm, buf, cap);
+  return gemm_plan_line(plan_gemm(q, k), q.has_norm, buf, cap);
+}
+
+int dsm_debug_gemm(dsm_engine* e, dsm_debug_gemm_args* g, char* plan, size_t plan_cap) {
+  if (!e) return DSM_ERR_INVALID;
+  auto bad = [&](const char* what) { e->set_error("dsm_debug_gemm: %s", what); return DSM_ERR_INVALID; };
+  if (!g || !plan || !plan_cap) return bad("null argument");
+  const int M = g->M, N = g->N, K = g->K, epi = g->epi;
+  if (M < 1 || N < 1 || K < 1 || M > (1 << 20) || N > (1 << 20) || K > (1 << 16)) return bad("M, N or K out of range");
+  if (epi == EPI_RVQ) return bad("the RVQ epilogue is not offered (the model tests keep it)");
+  if (epi != EPI_STORE && epi != EPI_QKV && epi != EPI_GATE) return bad("no such epilogue");
+  if (!g->X || !g->W || !(g->Y || (epi == EPI_STORE && g->Y2))) return bad("X, W and Y (the store epilogue: Y or Y2) are required");
+  const bool has_norm = g->norm_out != nullptr;
+  if (has_norm && !g->Y) return bad("a row norm needs Y");
+  if (epi != EPI_STORE && (g->bias || g->scale || g->res || g->Y2 || has_norm || g->act)) return bad("only the store epilogue has bias, act, scale, res, Y2 and a norm");
+  if (epi == EPI_QKV && !g->may_defer) return bad("the direct QKV epilogue is not offered (the model tests keep it)");
+  if (g->act != 0 && g->act != 1) return bad("act is 0 or 1");
+  if (has_norm && (!g->norm_w || (!g->norm_rms && !g->norm_b) || N % 4 != 0 || g->ymap.bstride != 0 || g->ymap.toff != 0 || g->ymap.ld != N ||
+                   g->norm_len < (uint64_t)M * N))
+    return bad("a row norm needs its weights, N % 4 == 0, Y as a plain [M][N] matrix and norm_len >= M * N");
+  // every row the kernels read or write lies inside the caller's buffers
+  const size_t x_ext = debug_extent(g->xmap, M, K);
+  if (!x_ext || x_ext > g->x_len) return bad("X rows reach outside x_len");
+  if (g->Y) {
+    const size_t ext = debug_extent(g->ymap, M, N);
+    if (!ext || ext > g->y_len || !debug_rows_disjoint(g->ymap, M, N)) return bad("Y rows overlap or reach outside y_len");
+  }
+  if (g->Y2) {
+    const size_t ext = debug_extent(g->y2map, M, N);
+    if (!ext || ext > g->y2_len || !debug_rows_disjoint(g->y2map, M, N)) return bad("Y2 rows overlap or reach outside y2_len");
+  }
+  if (g->res) {
+    const size_t ext = debug_extent(g->rmap, M, N);
+    if (!ext || ext > g->res_len) return bad("res rows reach outside res_len");
+  }
+  HIPCHK(hipSetDevice(e->device));
+  ApiShared api(e);
+  ApiExclusive alone(e);  // the knobs below are the engine's: nobody else launches while they are changed
+  if (int rc = dsm_sync(e)) return rc;
+
+  // the knobs for this call; put back on every way out
+  struct Restore {
+    DsmDevice* e;
+    GemmKnobs k;
+    DsmDevice::WeightMode wmode;
+    ~Restore() {
+      e->dot_mode = k.dot_mode; e->chunk_loop_min_tiles = k.chunk_loop_min_tiles; e->smallk_min_tiles = k.smallk_min_tiles;
+      e->smallk_mt = k.smallk_mt; e->loop_depth = k.loop_depth;
+      e->wmode = wmode;
+    }
+  } restore{e, gemm_knobs(e), e->wmode};
+  GemmKnobs k = restore.k;
+  if (!debug_knobs(g->knobs, &k)) return bad("knobs: dot_mode 0 / 1, smallk_mt 1 / 2 / 4, loop_depth 2 / 4");
+  e->dot_mode = k.dot_mode; e->chunk_loop_min_tiles = k.chunk_loop_min_tiles; e->smallk_min_tiles = k.smallk_min_tiles;
+  e->smallk_mt = k.smallk_mt; e->loop_depth = k.loop_depth;
+
+  // the weight, packed as load time packs it, in plain device memory of this call
+  struct TmpLinear {
+    DsmDevice* e;
+    Linear L;
+    ~TmpLinear() { e->dfree(L.w); e->dfree(L.bias); }
+  } w{e, Linear{}};
+  const bool gate = epi == EPI_GATE, bf16 = g->weight_bf16 != 0;
+  e->wmode = DsmDevice::W_PLAIN;
+  if (int rc = pack_linear(e, &w.L, g->W, gate ? 2 * N : N, K, bf16, g->bias, gate ? N : 0)) return rc;
+  e->wmode = restore.wmode;
+  const size_t w_bytes = (size_t)w.L.Npad * w.L.Kpad * (bf16 ? 2 : 4);
+  std::vector<uint8_t> w_before(w_bytes), w_after(w_bytes);
+  HIPCHK(hipMemcpy(w_before.data(), w.L.w, w_bytes, hipMemcpyDeviceToHost));
+
+  DebugBuf X(e), Y(e), Y2(e), res(e), scale(e), nw(e), nb(e), nout(e);
+  if (int rc = X.put(g->X, g->x_len)) return rc;
+  if (g->Y) if (int rc = Y.put(g->Y, g->y_len)) return rc;
+  if (g->Y2) if (int rc = Y2.put(g->Y2, g->y2_len)) return rc;
+  if (g->res) if (int rc = res.put(g->res, g->res_len)) return rc;
+  if (g->scale) if (int rc = scale.put(g->scale, N)) return rc;
+  if (has_norm) {
+    if (int rc = nw.put(g->norm_w, N)) return rc;
+    if (!g->norm_rms) if (int rc = nb.put(g->norm_b, N)) return rc;
+    if (int rc = nout.put(g->norm_out, g->norm_len)) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(nullptr));  // the copies above ran on the null stream, which the engine's streams do not wait for
+
+  GemmArgs a = base_args(w.L, X.d, debug_map(g->xmap), M);
+  a.N = N;
+  if (gate) a.nt_stride = N;
+  a.scale = scale.d;
+  a.act = g->act;
+  a.res = res.d; a.rmap = debug_map(g->rmap);
+  a.Y = Y.d; a.ymap = debug_map(g->ymap);
+  a.Y2 = Y2.d; a.y2map = debug_map(g->y2map);
+  if (has_norm) set_norm(a, nw.d, nb.d, nout.d, g->norm_rms ? 1 : 0);
+  const bool aligned = g->xmap.ld % 4 == 0 && g->xmap.bstride % 4 == 0;
+
+  // launch_gemm's own question, asked first: the plan line to hand back, and whether the plan ends in an epilogue the aid offers
+  const GemmPlan p = plan_gemm(gemm_query(a, bf16, epi, gate ? 2 : 1, aligned, g->may_defer != 0), k);
+  gemm_plan_line(p, has_norm, plan, plan_cap);
+  if (p.form == GEMM_NO_FIT) return bad("chunk partials do not fit in LDS");
+  // The generic kernel's chunk partials may plan up to 160 KB of dynamic LDS (K > 16384 at MT = 1), but launch_gemm does not raise the
+  // kernel's dynamic-LDS limit above the 64 KB every kernel starts with (only the attention launch does), and no engine has a product
+  // that large on the generic kernel: what such a launch does has never been run, so the aid does not offer it.
+  if (p.lds > 64 * 1024) return bad("a plan with more than 64 KB of dynamic LDS is not offered (launch_gemm never raises the kernel's limit)");
+  if (epi == EPI_QKV && p.reduce != GEMM_RED_CONSUMER) return bad("the direct QKV epilogue is not offered (the model tests keep it)");
+
+  hipStream_t st = e->s_model;
+  Slabs slabs;
+  Slabs* sp = g->may_defer ? &slabs : nullptr;
+  int rc;
+  if (epi == EPI_QKV) rc = bf16 ? launch_gemm<uint16_t, float, EPI_QKV, 1>(e, st, a, aligned, sp) : launch_gemm<float, float, EPI_QKV, 1>(e, st, a, aligned, sp);
+  else if (gate) rc = bf16 ? launch_gemm<uint16_t, float, EPI_GATE, 2>(e, st, a, aligned, sp) : launch_gemm<float, float, EPI_GATE, 2>(e, st, a, aligned, sp);
+  else rc = bf16 ? launch_gemm<uint16_t, float, EPI_STORE, 1>(e, st, a, aligned, sp) : launch_gemm<float, float, EPI_STORE, 1>(e, st, a, aligned, sp);
+  if (rc) return rc;
+  if (slabs.ws) {
+    const long n = (long)M * (N >> 2);
+    hipLaunchKernelGGL(debug_slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Y.d, a.ymap, slabs, M, N);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(st));
+
+  if (g->Y) HIPCHK(hipMemcpy(g->Y, Y.d, sizeof(float) * g->y_len, hipMemcpyDeviceToHost));
+  if (g->Y2) HIPCHK(hipMemcpy(g->Y2, Y2.d, sizeof(float) * g->y2_len, hipMemcpyDeviceToHost));
+  if (has_norm) HIPCHK(hipMemcpy(g->norm_out, nout.d, sizeof(float) * g->norm_len, hipMemcpyDeviceToHost));
+  if (g->x_back) HIPCHK(hipMemcpy(g->x_back, X.d, sizeof(float) * g->x_len, hipMemcpyDeviceToHost));
+  if (g->res && g->res_back) HIPCHK(hipMemcpy(g->res_back, res.d, sizeof(float) * g->res_len, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(w_after.data(), w.L.w, w_bytes, hipMemcpyDeviceToHost));
+  g->w_changed = w_before != w_after;
+  return 0;
 }
 
 }  // extern "C"

@@ -1110,6 +1110,48 @@ __global__ __launch_bounds__(256) void row_norm_kernel(float* __restrict__ y, co
   row_norm_apply(v, s, s2, d, eps, rms, w, b, y + (long)row * d);
 }
 
+// The same norm for a row wider than the 1024 * DSM_ROW_ITS elements row_norm_kernel keeps in registers (it would leave the rest
+// of such a row out of the sums and unwritten): the row is read twice, sums first.  Same canonical order — thread t chains its
+// elements 1024 * it + 4 * t + j over every it — and row_norm_apply's arithmetic.  No shipped model is this wide; the GEMM
+// launcher takes this kernel for a row norm behind a product with N > 4096 (d % 4 == 0 as above).
+__global__ __launch_bounds__(256) void row_norm_wide_kernel(float* __restrict__ y, const float* __restrict__ x,
+                                                            const float* __restrict__ w, const float* __restrict__ b, int rows,
+                                                            int d, float eps, int rms) {
+  __shared__ float red[8];
+  const float* xr = x + (long)blockIdx.x * d;
+  float* yr = y + (long)blockIdx.x * d;
+  float s = 0.0f, s2 = 0.0f;
+  for (int i = 4 * (int)threadIdx.x; i < d; i += 1024) {
+    const float4 v = *reinterpret_cast<const float4*>(xr + i);
+    s = s + v.x; s2 = DSM_FMAF(v.x, v.x, s2);
+    s = s + v.y; s2 = DSM_FMAF(v.y, v.y, s2);
+    s = s + v.z; s2 = DSM_FMAF(v.z, v.z, s2);
+    s = s + v.w; s2 = DSM_FMAF(v.w, v.w, s2);
+  }
+  block_row_sums(s, s2, red);
+  float mm = 1.f, mean = 0.f, inv = 0.f;
+  if (rms) {
+    mm = sqrtf(s2 / (float)d + eps);
+  } else {
+    mean = s / (float)d;
+    float var = s2 / (float)d - mean * mean;
+    inv = 1.0f / sqrtf(var + eps);
+  }
+  for (int i = 4 * (int)threadIdx.x; i < d; i += 1024) {
+    const float4 v = *reinterpret_cast<const float4*>(xr + i);
+    const float4 wv = *reinterpret_cast<const float4*>(w + i);
+    float4 o;
+    if (rms) {
+      o.x = (v.x / mm) * wv.x; o.y = (v.y / mm) * wv.y; o.z = (v.z / mm) * wv.z; o.w = (v.w / mm) * wv.w;
+    } else {
+      const float4 bv = *reinterpret_cast<const float4*>(b + i);
+      o.x = ((v.x - mean) * inv) * wv.x + bv.x; o.y = ((v.y - mean) * inv) * wv.y + bv.y;
+      o.z = ((v.z - mean) * inv) * wv.z + bv.z; o.w = ((v.w - mean) * inv) * wv.w + bv.w;
+    }
+    *reinterpret_cast<float4*>(yr + i) = o;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Attention over the ring cache — core/batched_transformer.rs:107-113 + mask semantics of
 // core/kv_cache.rs:119-237 in closed form: slot j is visible to query t iff

@@ -699,6 +699,63 @@ enum {
   DSM_GEMMQ_MAY_DEFER = 1 << 10 /* the caller's next kernel can sum split-K slabs itself */
 };
 int dsm_debug_gemm_plan(int stt, int dot_mode, int weight_bf16, int epi, int nt, int M, int N, int K, int flags, char* buf, size_t cap);
+/* The same with the five numbers the decision reads given one by one: knobs = {dot_mode, chunk_loop_min_tiles, smallk_min_tiles,
+ * smallk_mt, loop_depth} (GemmKnobs, csrc/dsm_gemm_plan.h); an entry of -1 takes what an engine of the given kind starts from
+ * (for dot_mode: 0).  What dsm_debug_gemm below will run for the same shape, flags and knobs. */
+int dsm_debug_gemm_plan_knobs(int stt, const int* knobs, int weight_bf16, int epi, int nt, int M, int N, int K, int flags, char* buf, size_t cap);
+
+/* TEST AID, not a serving call: one matrix product through the engine's own GEMM launcher (launch_gemm), on the model stream,
+ * eagerly, outside any graph — so that every kernel form the launcher can choose is run alone against a reference
+ * (tests/test_gemm_kernels_gpu.py).  Y = epilogue(X W^T) for M rows of X, a weight W [N][K] in f32 on the host (the gate:
+ * [2 N][K], gate rows first, N = the hidden width) that is packed the way a checkpoint's weights are (bf16 weights rounded and
+ * fragment-major, the gate with its split row), into plain device memory that is released before the call returns — never into
+ * the weight arena.  Row r of a matrix starts at element (r / rpb) * bstride + (r % rpb + toff) * ld of its buffer, as in the
+ * engine (RowMap): overlapping rows (a convolution over its concat buffer: K > ld), an offset into a concat buffer and rows off
+ * a 16-byte boundary can all be said.  Every buffer is copied to the device whole, and Y, Y2 and norm_out are copied back whole:
+ * what the caller put outside the M x N result must still be there.
+ *   epi       0 store: bias, act (1 = gelu_erf), LayerScale `scale`, residual `res`, Y and / or its ELU copy Y2, a row norm of Y
+ *             (norm_w, norm_b unless norm_rms, norm_out [M][N]; Y is then a plain [M][N] matrix and N % 4 == 0);
+ *             2 gate: Y = silu(g) * u, nothing else;
+ *             1 QKV: offered only where the plan leaves the split-K slabs to the consumer (may_defer), see below — the direct
+ *             QKV epilogue (RoPE + ring scatter) and the RVQ epilogue (3) are refused: the model tests keep those.
+ *   may_defer the caller could sum split-K slabs itself.  Where the plan then says reduce=consumer the aid sums the slabs with the
+ *             library's own ordered slab sum into Y: a plain [M][N] product.
+ *   knobs     as for dsm_debug_gemm_plan_knobs, -1 = the engine's own; set for this call and restored after it.
+ *   x_back / res_back (optional, x_len / res_len floats): the device copies of X / res after the run; w_changed: 1 when the
+ *             packed weight on the device is not what it was before the launch.
+ * Also refused: a plan with more than 64 KB of dynamic LDS (the generic kernel at K > 16384) — the launcher never raises a GEMM
+ * kernel's dynamic-LDS limit and no engine has such a product, so that launch has never been run.
+ * plan receives the line of the plan that ran (as dsm_debug_gemm_plan writes it).  No DSM_* variable is read, nothing differs in
+ * any launch of an engine on which this is never called, and the engine steps afterwards as before.  Returns 0 or <0. */
+typedef struct dsm_debug_rowmap {
+  int64_t bstride;
+  int32_t rpb, ld, toff, pad_;
+} dsm_debug_rowmap;
+typedef struct dsm_debug_gemm_args {
+  int32_t M, N, K;
+  int32_t weight_bf16, epi, act, may_defer, norm_rms;
+  int32_t knobs[5];
+  int32_t w_changed; /* out */
+  const float* X;
+  uint64_t x_len;
+  dsm_debug_rowmap xmap;
+  const float* W;
+  const float *bias, *scale; /* [N] or null */
+  const float* res;
+  uint64_t res_len;
+  dsm_debug_rowmap rmap;
+  float* Y; /* in: what the buffer holds before, out: after */
+  uint64_t y_len;
+  dsm_debug_rowmap ymap;
+  float* Y2;
+  uint64_t y2_len;
+  dsm_debug_rowmap y2map;
+  const float *norm_w, *norm_b; /* [N] */
+  float* norm_out;              /* in / out, norm_len floats, rows of N from element 0 */
+  uint64_t norm_len;
+  float *x_back, *res_back;
+} dsm_debug_gemm_args;
+int dsm_debug_gemm(dsm_engine*, dsm_debug_gemm_args* args, char* plan, size_t plan_cap);
 
 /* ------------------------------------------------------------------------------------------------
  * Audio ingest helpers (host only; SURVEY.md §8(f) rank 3, first part).

@@ -2019,5 +2019,11 @@ float orc_gelu_erf(float x) { return dsm_gelu_erf(x); }
 void orc_sincosf(float x, float* s, float* c) { dsm_sincosf(x, s, c); }
 uint16_t orc_f32_to_bf16(float x) { return dsm_f32_to_bf16(x); }
 float orc_bf16_to_f32(uint16_t h) { return dsm_bf16_to_f32(h); }
+/* the same functions over n values (tests/gemm_ref.py: a GEMM epilogue over a whole output) */
+void orc_map_f32(int fn, float* y, const float* x, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    y[i] = fn == ORC_MAP_ELU ? dsm_elu(x[i]) : fn == ORC_MAP_SILU ? dsm_silu(x[i]) : fn == ORC_MAP_GELU_ERF ? dsm_gelu_erf(x[i])
+                                                                                   : dsm_bf16_to_f32(dsm_f32_to_bf16(x[i]));
+}
 
 #include "dsm_oracle_tts.inc"

@@ -99,6 +99,8 @@ float orc_gelu_erf(float x);
 void orc_sincosf(float x, float* s, float* c);
 uint16_t orc_f32_to_bf16(float x);
 float orc_bf16_to_f32(uint16_t h);
+enum { ORC_MAP_ELU = 0, ORC_MAP_SILU = 1, ORC_MAP_GELU_ERF = 2, ORC_MAP_BF16_ROUND = 3 };
+void orc_map_f32(int fn, float* y, const float* x, size_t n); /* y[i] = fn(x[i]); BF16_ROUND: to bf16 and back */
 #ifdef __cplusplus
 }
 #endif

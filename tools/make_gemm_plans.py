@@ -182,22 +182,55 @@ def mimi_products(m, B, stt=1, dot_mode=1):
     return rows
 
 
+def stt_lm_products(rows, name, cfg, M, dot_mode=1):
+    """The LM products of one STT stream group of M rows: one layer, the text head, the extra heads where the preset has any."""
+    d = cfg.lm.d_model
+    transformer(rows, name + ":", 1, dot_mode, 1, M, 1, d, gating_hidden(cfg.lm), True, post_norm=True)
+    add(rows, name + ": text linear", 1, dot_mode, 1, STORE, 1, M, cfg.text_out_vocab_size, d, BASE | Y)
+    if cfg.extra_heads_num:
+        add(rows, name + ": extra heads", 1, dot_mode, 1, STORE, 1, M, cfg.extra_heads_num * cfg.extra_heads_dim, d, BASE | Y)
+
+
+def tts_lm_products(rows, name, cfg, M, dot_mode=1):
+    """The products of one TTS stream group of M batch rows: one main-LM layer, the text head, the depformer."""
+    d, D = cfg.lm.d_model, cfg.depformer.d_model
+    transformer(rows, name + " main LM:", 0, dot_mode, 1, M, 1, d, gating_hidden(cfg.lm), True, post_norm=True, ca=True)
+    add(rows, name + " text linear", 0, dot_mode, 1, STORE, 1, M, cfg.text_out_vocab_size, d, BASE | Y)
+    add(rows, name + " depformer in_all", 0, dot_mode, 1, STORE, 1, M, cfg.dep_weight_groups * D, d, BASE | Y)
+    transformer(rows, name + " depformer:", 0, dot_mode, 1, M, 1, D, gating_hidden(cfg.depformer), True)
+    add(rows, name + " depformer linears.k", 0, dot_mode, 1, STORE, 1, M, cfg.audio_vocab_size - 1, D, BASE | Y | MAY_DEFER)
+
+
+def stt_group_rows(B):
+    """Rows per LM launch of an STT engine of B slots: two stream groups of whole 16-row blocks from B = 32 on (dsm_asr_create)."""
+    G = min(2 if B >= 32 else 1, (B + 15) // 16)
+    n16, out, b0 = (B + 15) // 16, [], 0
+    for g in range(G):
+        nb = min((n16 // G + (1 if g < n16 % G else 0)) * 16, B - b0)
+        out.append(nb)
+        b0 += nb
+    return out
+
+
+def tts_group_rows(B, rows_per_slot):
+    """Rows per launch of a TTS engine of B slots: one stream group below 96 slots, two from there on (dsm_tts_create)."""
+    G = min(2 if B >= 96 else 1, B)
+    return [(B // G + (1 if g < B % G else 0)) * rows_per_slot for g in range(G)]
+
+
 def preset_rows():
     """(b) the products of the shipped presets."""
     rows = []
     stt = dsm_amd.config_stt_1b_en_fr()
-    d, hid = stt.lm.d_model, gating_hidden(stt.lm)
-    transformer(rows, "stt-1b group of 32:", 1, 1, 1, 32, 1, d, hid, True, post_norm=True)
-    add(rows, "stt-1b group of 32: text linear", 1, 1, 1, STORE, 1, 32, stt.text_out_vocab_size, d, BASE | Y)
-    add(rows, "stt-1b group of 32: extra heads", 1, 1, 1, STORE, 1, 32, stt.extra_heads_num * stt.extra_heads_dim, d, BASE | Y)
+    stt_lm_products(rows, "stt-1b group of 32", stt, 32)
     rows += mimi_products(stt.mimi, 64)
     tts = dsm_amd.config_tts_v202501()
-    d, hid, D, dhid = tts.lm.d_model, gating_hidden(tts.lm), tts.depformer.d_model, gating_hidden(tts.depformer)
-    transformer(rows, "tts B = 32 main LM:", 0, 1, 1, 32, 1, d, hid, True, post_norm=True, ca=True)
-    add(rows, "tts B = 32 text linear", 0, 1, 1, STORE, 1, 32, tts.text_out_vocab_size, d, BASE | Y)
-    add(rows, "tts B = 32 depformer in_all", 0, 1, 1, STORE, 1, 32, tts.dep_weight_groups * D, d, BASE | Y)
-    transformer(rows, "tts B = 32 depformer:", 0, 1, 1, 32, 1, D, dhid, True)
-    add(rows, "tts B = 32 depformer linears.k", 0, 1, 1, STORE, 1, 32, tts.audio_vocab_size - 1, D, BASE | Y | MAY_DEFER)
+    tts_lm_products(rows, "tts B = 32", tts, 32)
+    # the groups of 64 rows (batch 128, the batch BASELINE.json quotes stt-2.6b-en at) and the second STT preset
+    stt_lm_products(rows, "stt-1b group of 64", stt, 64)
+    big = dsm_amd.config_stt_2_6b_en()
+    stt_lm_products(rows, "stt-2.6b group of 32", big, 32)
+    stt_lm_products(rows, "stt-2.6b group of 64", big, 64)
     return rows
 
 
@@ -206,6 +239,16 @@ def plan_line(lib, r):
     buf = C.create_string_buffer(512)
     n = lib.dsm_debug_gemm_plan(r["stt"], r["dot_mode"], r["weight_bf16"], r["epi"], r["nt"], r["M"], r["N"], r["K"], r["flags"], buf, len(buf))
     assert n > 0, r
+    return buf.value.decode()
+
+
+def plan_line_knobs(lib, r, knobs):
+    """The same under explicit knobs (dot_mode, chunk_loop_min_tiles, smallk_min_tiles, smallk_mt, loop_depth; -1 = the default of
+    the row's engine kind): dsm_debug_gemm_plan_knobs.  knobs[0] decides the mode, not the row's dot_mode."""
+    buf = C.create_string_buffer(512)
+    n = lib.dsm_debug_gemm_plan_knobs(r["stt"], (C.c_int * 5)(*knobs), r["weight_bf16"], r["epi"], r["nt"], r["M"], r["N"], r["K"], r["flags"],
+                                      buf, len(buf))
+    assert n > 0, (r, knobs)
     return buf.value.decode()
 
 
