@@ -1058,18 +1058,24 @@ def wav_decode(data):
         lib.dsm_free(ptr)
 
 
-def ingest_describe(rate, fmt):
-    """dsm_ingest_describe: the descriptor of an input format (csrc/dsm_ingest.h) as a dict — rate, fmt, L, M, half, taps, F_in,
-    frame_bytes, D (the latency in 24 kHz samples), table_words.  DsmError with the reason for a rate or format outside the
-    definition."""
+def _pcm_describe(call, frame_key, rate, fmt):
+    """dsm_ingest_describe / dsm_egress_describe: the twelve descriptor words of a format (csrc/dsm_pcm_format.h) as a dict, the
+    frame length under the direction's own key, without the table offset and the reserved word."""
     lib = load_library()
     w = np.zeros(12, dtype=np.uint32)
-    rc = lib.dsm_ingest_describe(int(rate), int(fmt), _ptr(w))
+    rc = getattr(lib, call)(int(rate), int(fmt), _ptr(w))
     if rc != 0:
         msg = lib.dsm_last_error(None)
-        raise DsmError(f"dsm_ingest_describe failed ({rc}): {msg.decode() if msg else '?'}")
-    names = ("rate", "fmt", "L", "M", "half", "taps", "F_in", "frame_bytes", "D", "table_off", "table_words", "reserved")
+        raise DsmError(f"{call} failed ({rc}): {msg.decode() if msg else '?'}")
+    names = ("rate", "fmt", "L", "M", "half", "taps", frame_key, "frame_bytes", "D", "table_off", "table_words", "reserved")
     return {k: int(v) for k, v in zip(names, w) if k not in ("table_off", "reserved")}
+
+
+def ingest_describe(rate, fmt):
+    """dsm_ingest_describe: the descriptor of an input format (csrc/dsm_pcm_format.h, DSM_PCM_IN) as a dict — rate, fmt, L, M,
+    half, taps, F_in, frame_bytes, D (the latency in 24 kHz samples), table_words.  DsmError with the reason for a rate or format
+    outside the definition."""
+    return _pcm_describe("dsm_ingest_describe", "F_in", rate, fmt)
 
 
 def ingest_g711_table(fmt):
@@ -1080,34 +1086,30 @@ def ingest_g711_table(fmt):
     return out
 
 
-class ingest_host:
-    """dsm_ingest_host_*: one slot's streaming ingest on the host — the function ingest_resample_kernel is bit-identical to.
-    step(raw) takes one frame (bytes, or an array whose bytes are the frame: frame_bytes of them) and returns the 1920 samples
-    at 24 kHz the step hands Mimi."""
+class _pcm_host:
+    """What ingest_host and egress_host share: the format's descriptor, the C state and its release.  A subclass names its
+    calls (`_side`) and its describe function's frame key, and adds step()."""
+    _side = _frame_key = None
 
     def __init__(self, rate, fmt=PCM_F32):
         self.lib = load_library()
-        self.info = ingest_describe(rate, fmt)  # raises with the reason for an unsupported format
-        self.frame_samples, self.frame_bytes, self.latency = self.info["F_in"], self.info["frame_bytes"], self.info["D"]
-        self.h = self.lib.dsm_ingest_host_new(int(rate), int(fmt))
+        self.info = _pcm_describe(f"dsm_{self._side}_describe", self._frame_key, rate, fmt)  # raises with the reason for an unsupported format
+        self.frame_samples, self.frame_bytes, self.latency = self.info[self._frame_key], self.info["frame_bytes"], self.info["D"]
+        self.h = getattr(self.lib, f"dsm_{self._side}_host_new")(int(rate), int(fmt))
         if not self.h:
             msg = self.lib.dsm_last_error(None)
-            raise DsmError(f"dsm_ingest_host_new failed: {msg.decode() if msg else '?'}")
+            raise DsmError(f"dsm_{self._side}_host_new failed: {msg.decode() if msg else '?'}")
 
-    def step(self, raw):
-        raw = raw if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw).tobytes()
-        if len(raw) != self.frame_bytes:
-            raise DsmError(f"ingest_host.step: a frame of {len(raw)} bytes, the format's frame has {self.frame_bytes}")
-        out = np.zeros(FRAME_SIZE, dtype=np.float32)
-        rc = self.lib.dsm_ingest_host(self.h, bytes(raw), _ptr(out))
+    def _step(self, src, out):
+        rc = getattr(self.lib, f"dsm_{self._side}_host")(self.h, src, _ptr(out))
         if rc != 0:
             msg = self.lib.dsm_last_error(None)
-            raise DsmError(f"dsm_ingest_host failed ({rc}): {msg.decode() if msg else '?'}")
+            raise DsmError(f"dsm_{self._side}_host failed ({rc}): {msg.decode() if msg else '?'}")
         return out
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.dsm_ingest_host_free(self.h)
+            getattr(self.lib, f"dsm_{self._side}_host_free")(self.h)
             self.h = None
 
     def __del__(self):
@@ -1117,18 +1119,24 @@ class ingest_host:
             pass
 
 
+class ingest_host(_pcm_host):
+    """dsm_ingest_host_*: one slot's streaming ingest on the host — the function ingest_resample_kernel is bit-identical to.
+    step(raw) takes one frame (bytes, or an array whose bytes are the frame: frame_bytes of them) and returns the 1920 samples
+    at 24 kHz the step hands Mimi."""
+    _side, _frame_key = "ingest", "F_in"
+
+    def step(self, raw):
+        raw = raw if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw).tobytes()
+        if len(raw) != self.frame_bytes:
+            raise DsmError(f"ingest_host.step: a frame of {len(raw)} bytes, the format's frame has {self.frame_bytes}")
+        return self._step(bytes(raw), np.zeros(FRAME_SIZE, dtype=np.float32))
+
+
 def egress_describe(rate, fmt):
-    """dsm_egress_describe: the descriptor of an output format (csrc/dsm_egress.h) as a dict — rate, fmt, L, M, half, taps,
-    F_out, frame_bytes, D (the latency in output samples), table_words.  DsmError with the reason for a rate or format outside
-    the definition."""
-    lib = load_library()
-    w = np.zeros(12, dtype=np.uint32)
-    rc = lib.dsm_egress_describe(int(rate), int(fmt), _ptr(w))
-    if rc != 0:
-        msg = lib.dsm_last_error(None)
-        raise DsmError(f"dsm_egress_describe failed ({rc}): {msg.decode() if msg else '?'}")
-    names = ("rate", "fmt", "L", "M", "half", "taps", "F_out", "frame_bytes", "D", "table_off", "table_words", "reserved")
-    return {k: int(v) for k, v in zip(names, w) if k not in ("table_off", "reserved")}
+    """dsm_egress_describe: the descriptor of an output format (csrc/dsm_pcm_format.h, DSM_PCM_OUT) as a dict — rate, fmt, L, M,
+    half, taps, F_out, frame_bytes, D (the latency in output samples), table_words.  DsmError with the reason for a rate or
+    format outside the definition."""
+    return _pcm_describe("dsm_egress_describe", "F_out", rate, fmt)
 
 
 def egress_encode_sample(fmt, v):
@@ -1141,40 +1149,16 @@ def egress_encode_sample(fmt, v):
     return int(out[:2].view("<i2")[0]) if fmt == PCM_S16 else int(out[0])
 
 
-class egress_host:
+class egress_host(_pcm_host):
     """dsm_egress_host_*: one slot's streaming egress on the host — the function egress_resample_kernel is bit-identical to.
     step(frame) takes one emitted frame of 1920 f32 samples at 24 kHz and returns the format's frame as frame_bytes uint8."""
-
-    def __init__(self, rate, fmt=PCM_F32):
-        self.lib = load_library()
-        self.info = egress_describe(rate, fmt)  # raises with the reason for an unsupported format
-        self.frame_samples, self.frame_bytes, self.latency = self.info["F_out"], self.info["frame_bytes"], self.info["D"]
-        self.h = self.lib.dsm_egress_host_new(int(rate), int(fmt))
-        if not self.h:
-            msg = self.lib.dsm_last_error(None)
-            raise DsmError(f"dsm_egress_host_new failed: {msg.decode() if msg else '?'}")
+    _side, _frame_key = "egress", "F_out"
 
     def step(self, frame):
         frame = np.ascontiguousarray(frame, dtype=np.float32)
         if frame.size != FRAME_SIZE:
             raise DsmError(f"egress_host.step: a frame of {frame.size} samples, a step has {FRAME_SIZE}")
-        out = np.zeros(self.frame_bytes, dtype=np.uint8)
-        rc = self.lib.dsm_egress_host(self.h, _ptr(frame), _ptr(out))
-        if rc != 0:
-            msg = self.lib.dsm_last_error(None)
-            raise DsmError(f"dsm_egress_host failed ({rc}): {msg.decode() if msg else '?'}")
-        return out
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.dsm_egress_host_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._step(_ptr(frame), np.zeros(self.frame_bytes, dtype=np.uint8))
 
 
 class LinearResampler:

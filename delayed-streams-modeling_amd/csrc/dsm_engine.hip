@@ -27,6 +27,7 @@
 #include "dsm_config_presets.h"
 #include "dsm_gemm_plan.h"
 #include "dsm_kernels.h"
+#include "dsm_pcm_table.inc"
 #include "dsm_numerics.h"
 #include "dsm_safetensors.h"
 #include "dsm_slot_blob.h"
@@ -315,23 +316,18 @@ struct dsm_engine : DsmDevice {
   std::vector<int> bias_slot_handle;  // [B], 0 = none
   int bias_next_handle = 1;
   std::mutex bias_mu;  // the host side of the section (the worker's threads both reach it)
-  // ingest (dsm_asr_set_ingest; dsm_ingest.h): the switch, and what ingest_resample_kernel reads — the format descriptors
-  // [kIngestFormats] (entry 0 = 24000 / F32, append-only: one per (rate, format) ever set), the coefficient arena (append-only:
-  // one phase table per rate), the G.711 tables, each slot's descriptor index [B]; per Mimi side the history [B][136], the
-  // "started" words [B] and the device copy of the raw rows [B][15360].  Pinned: one raw staging per side and per ticket.
-  // All of it allocated by the first dsm_asr_set_ingest(1).  Host side: mirrors of the descriptors and of the slots' indices.
-  static constexpr size_t kIngestFormats = 64, kIngestCoefWords = (size_t)1 << 20;
-  bool ingest_on = false, ingest_ready = false;
-  dsm_ingest_desc* ingest_descs_d = nullptr;
-  float *ingest_coef_d = nullptr, *ingest_g711_d = nullptr;
-  uint32_t* ingest_slot_desc_d = nullptr;
+  // ingest (dsm_asr_set_ingest; dsm_pcm_format.h): the switch, and what ingest_resample_kernel reads — the slots' formats
+  // (PcmFormatTable, dsm_pcm_table.inc: descriptors, coefficient arena, each slot's descriptor index, with their host mirrors),
+  // the G.711 tables; per Mimi side the history [B][136], the "started" words [B] and the device copy of the raw rows
+  // [B][15360].  Pinned: one raw staging per side and per ticket.  All of it allocated by the first dsm_asr_set_ingest(1),
+  // after which ingest_fmt.ready holds.
+  bool ingest_on = false;
+  PcmFormatTable ingest_fmt{DSM_PCM_IN};
+  float* ingest_g711_d = nullptr;
   float* ingest_hist[2] = {};
   uint32_t* ingest_started[2] = {};
   uint8_t *ingest_raw_d[2] = {}, *ingest_raw_h[2] = {}, *ingest_pipe_raw_h[4] = {};
-  std::vector<dsm_ingest_desc> ingest_descs_h;
-  std::vector<uint32_t> ingest_slot_desc_h;
-  size_t ingest_coef_used = 0;
-  std::mutex ingest_mu;  // the host mirrors (the worker's threads both reach them)
+  std::mutex ingest_mu;  // the table's host mirrors (the worker's threads both reach them)
   dsm_metrics metrics{};
   // run-ahead pipeline between the encoder thread and the model thread (dsm_mimi_encode_step_async /
   // dsm_asr_step_tokens_ticket): the reference's sync_channel(100) of PipelineMsg (srv/batched_asr.rs:291), here a ring of

@@ -732,7 +732,7 @@ int reset_mimi_slot(dsm_engine* e, int side, hipStream_t st, int slot) {  // Mim
   MimiState& s = e->mimi[side];
   if (int rc = reset_transformer_slot(e, st, s.tr, slot)) return rc;
   // ingest: the side's history of the slot is cleared (a slot that has not started reads zeros); its format stays
-  if (e->ingest_ready) HIPCHK(hipMemsetAsync(e->ingest_started[side] + slot, 0, sizeof(uint32_t), st));
+  if (e->ingest_fmt.ready) HIPCHK(hipMemsetAsync(e->ingest_started[side] + slot, 0, sizeof(uint32_t), st));
   if (!s.h_descs.empty()) {
     hipLaunchKernelGGL(conv_state_reset_kernel, dim3((unsigned)s.h_descs.size()), dim3(256), 0, st, s.descs, slot);
     HIPCHK(hipGetLastError());

@@ -1,25 +1,23 @@
 // dsm_ingest.inc — the engine half of the ingest section of include/dsm.h (included by dsm_engine.hip behind
 // dsm_text_bias.inc): the switch and its allocations, the per-slot format, the raw entry points — each its plain sibling with
 // "upload 1920 floats per slot" replaced by "upload the raw rows, launch ingest_resample_kernel" — and the host functions.  The
-// definition and the checked descriptor are csrc/dsm_ingest.h; the kernel is ingest_resample_kernel (dsm_kernels.h);
-// reset_mimi_slot clears a side's history of a slot.
+// definition and the checked descriptor are csrc/dsm_pcm_format.h (DSM_PCM_IN); the slots' formats are a PcmFormatTable
+// (dsm_pcm_table.inc); the kernel is ingest_resample_kernel (dsm_kernels.h); reset_mimi_slot clears a side's history of a slot.
 
 struct dsm_ingest_host_state {
-  dsm_ingest::Host h;
+  dsm_pcm::Host h;
 };
 
 namespace {
 
-// The section's buffers, once per engine, under the exclusive side of api_mu (allocations never run beside a capture).
+// The section's buffers, once per engine, under the exclusive side of api_mu (allocations never run beside a capture).  The
+// format table comes last: its `ready` says that all of this is there.
 int ingest_ensure(dsm_engine* e) {
-  if (e->ingest_ready) return 0;
-  const size_t B = (size_t)e->B, rowb = DSM_INGEST_MAX_FRAME_BYTES;
-  if (int rc = e->dalloc(&e->ingest_descs_d, dsm_engine::kIngestFormats)) return rc;
-  if (int rc = e->dalloc(&e->ingest_coef_d, dsm_engine::kIngestCoefWords, false)) return rc;
-  if (int rc = e->upload(&e->ingest_g711_d, dsm_ingest::g711_tables(), (size_t)512)) return rc;
-  if (int rc = e->dalloc(&e->ingest_slot_desc_d, B)) return rc;  // zeroed: every slot on entry 0, the pass-through format
+  if (e->ingest_fmt.ready) return 0;
+  const size_t B = (size_t)e->B, rowb = DSM_PCM_MAX_FRAME_BYTES;
+  if (int rc = e->upload(&e->ingest_g711_d, dsm_pcm::g711_tables(), (size_t)512)) return rc;
   for (int side = 0; side < 2; ++side) {
-    if (int rc = e->dalloc(&e->ingest_hist[side], B * DSM_INGEST_MAX_TAPS)) return rc;
+    if (int rc = e->dalloc(&e->ingest_hist[side], B * DSM_PCM_MAX_TAPS_IN)) return rc;
     if (int rc = e->dalloc(&e->ingest_started[side], B)) return rc;
     if (int rc = e->dalloc(&e->ingest_raw_d[side], B * rowb)) return rc;
     if (int rc = e->halloc(&e->ingest_raw_h[side], B * rowb)) return rc;
@@ -27,56 +25,7 @@ int ingest_ensure(dsm_engine* e) {
   static_assert(dsm_engine::kPipe == 4, "ingest_pipe_raw_h");
   for (int i = 0; i < dsm_engine::kPipe; ++i)
     if (int rc = e->halloc(&e->ingest_pipe_raw_h[i], B * rowb)) return rc;
-  dsm_ingest_desc d0;
-  std::string err;
-  if (dsm_ingest::describe(DSM_INGEST_OUT_RATE, DSM_PCM_F32, &d0, &err)) { e->set_error("%s", err.c_str()); return DSM_ERR_INVALID; }
-  HIPCHK(hipMemcpy(e->ingest_descs_d, &d0, sizeof d0, hipMemcpyHostToDevice));
-  HIPCHK(hipStreamSynchronize(nullptr));
-  e->ingest_descs_h.assign(1, d0);
-  e->ingest_slot_desc_h.assign(B, 0u);
-  e->ingest_coef_used = 0;
-  e->ingest_ready = true;
-  return 0;
-}
-
-// the entry of (rate, fmt), made if it is new: the rate's phase table appended to the arena, the descriptor to the table.  New
-// entries are referenced by no slot, so no step in flight reads them: plain blocking copies.  Caller holds api_mu exclusively.
-int ingest_format_entry(dsm_engine* e, int rate, int fmt, uint32_t* index) {
-  dsm_ingest_desc d;
-  std::string err;
-  if (int rc = dsm_ingest::describe(rate, fmt, &d, &err)) { e->set_error("%s", err.c_str()); return rc; }
-  bool have_table = d.table_words == 0;
-  for (size_t i = 0; i < e->ingest_descs_h.size(); ++i) {
-    const dsm_ingest_desc& o = e->ingest_descs_h[i];
-    if (o.rate == d.rate && o.fmt == d.fmt) { *index = (uint32_t)i; return 0; }
-    if (o.rate == d.rate && !have_table) { d.table_off = o.table_off; have_table = true; }
-  }
-  if (e->ingest_descs_h.size() >= dsm_engine::kIngestFormats) {
-    e->set_error("input format: %d distinct formats are in use, no room for another", (int)dsm_engine::kIngestFormats);
-    return DSM_ERR_STATE;
-  }
-  if (!have_table) {
-    std::vector<float> ph;
-    if (dsm_ingest::phase_table(rate, DSM_INGEST_OUT_RATE, nullptr, nullptr, nullptr, &ph) || ph.size() != d.table_words) {
-      e->set_error("input format: no phase table for %d Hz", rate);
-      return DSM_ERR_INVALID;
-    }
-    if (e->ingest_coef_used + ph.size() > dsm_engine::kIngestCoefWords) {
-      e->set_error("input format: the coefficient arena is full (%zu of %zu words), no room for %d Hz", e->ingest_coef_used,
-                   dsm_engine::kIngestCoefWords, rate);
-      return DSM_ERR_STATE;
-    }
-    d.table_off = (uint32_t)e->ingest_coef_used;
-    HIPCHK(hipMemcpy(e->ingest_coef_d + d.table_off, ph.data(), sizeof(float) * ph.size(), hipMemcpyHostToDevice));
-    e->ingest_coef_used += ph.size();
-  }
-  if (int rc = dsm_ingest::check(&d, e->ingest_coef_used, &err)) { e->set_error("%s", err.c_str()); return rc; }
-  const size_t at = e->ingest_descs_h.size();
-  HIPCHK(hipMemcpy(e->ingest_descs_d + at, &d, sizeof d, hipMemcpyHostToDevice));
-  HIPCHK(hipStreamSynchronize(nullptr));
-  e->ingest_descs_h.push_back(d);
-  *index = (uint32_t)at;
-  return 0;
+  return e->ingest_fmt.ensure(e, B);
 }
 
 // a raw call's arguments against the slots' formats.  mask NULL: every slot counts (the mask is on the device)
@@ -85,20 +34,8 @@ int ingest_check_call(dsm_engine* e, size_t pitch, const uint8_t* mask) {
     e->set_error("ingest is off: dsm_asr_set_ingest(engine, 1) comes before the raw calls");
     return DSM_ERR_STATE;
   }
-  if (pitch == 0 || pitch % 16 != 0 || pitch > DSM_INGEST_MAX_FRAME_BYTES) {
-    e->set_error("raw frames: a pitch of %zu bytes (a multiple of 16, at most %u)", pitch, DSM_INGEST_MAX_FRAME_BYTES);
-    return DSM_ERR_INVALID;
-  }
   std::lock_guard<std::mutex> host(e->ingest_mu);
-  for (int b = 0; b < e->B; ++b) {
-    if (mask && !mask[b]) continue;
-    const dsm_ingest_desc& d = e->ingest_descs_h[e->ingest_slot_desc_h[(size_t)b]];
-    if (d.frame_bytes > pitch) {
-      e->set_error("raw frames: slot %d's frame has %u bytes, the pitch is %zu", b, d.frame_bytes, pitch);
-      return DSM_ERR_INVALID;
-    }
-  }
-  return 0;
+  return e->ingest_fmt.check_pitch(e, pitch, mask, mask == nullptr);
 }
 
 // d_raw [B][pitch] and d_mask [B] on the device -> the side's frames in MimiState::pcm and its histories
@@ -112,9 +49,9 @@ int ingest_launch(dsm_engine* e, int side, hipStream_t st, const uint8_t* d_raw,
   a.raw = d_raw;
   a.pitch = pitch;
   a.mask = d_mask;
-  a.slot_desc = e->ingest_slot_desc_d;
-  a.descs = e->ingest_descs_d;
-  a.coef = e->ingest_coef_d;
+  a.slot_desc = e->ingest_fmt.slot_desc_d;
+  a.descs = e->ingest_fmt.descs_d;
+  a.coef = e->ingest_fmt.coef_d;
   a.g711 = e->ingest_g711_d;
   a.hist = e->ingest_hist[side];
   a.started = e->ingest_started[side];
@@ -144,7 +81,7 @@ dsm_ingest_host_state* dsm_ingest_host_new(int sample_rate_hz, int sample_format
   dsm_ingest_host_state* s = new (std::nothrow) dsm_ingest_host_state();
   if (!s) return nullptr;
   std::string err;
-  if (dsm_ingest::host_new(sample_rate_hz, sample_format, &s->h, &err)) {
+  if (dsm_pcm::host_new(DSM_PCM_IN, sample_rate_hz, sample_format, &s->h, &err)) {
     g_create_error = err;
     delete s;
     return nullptr;
@@ -157,17 +94,17 @@ void dsm_ingest_host_free(dsm_ingest_host_state* s) { delete s; }
 int dsm_ingest_host(dsm_ingest_host_state* s, const void* raw_frame, float* out1920) {
   if (!s) return DSM_ERR_INVALID;
   std::string err;
-  const int rc = dsm_ingest::host_step(&s->h, raw_frame, s->h.d.frame_bytes, out1920, &err);
+  const int rc = dsm_pcm::host_step_in(&s->h, raw_frame, s->h.d.frame_bytes, out1920, &err);
   if (rc) g_create_error = err;
   return rc;
 }
 
 int dsm_ingest_describe(int sample_rate_hz, int sample_format, uint32_t* words12) {
   if (!words12) return DSM_ERR_INVALID;
-  dsm_ingest_desc d;
+  dsm_pcm_desc d;
   std::string err;
-  if (int rc = dsm_ingest::describe(sample_rate_hz, sample_format, &d, &err)) { g_create_error = err; return rc; }
-  static_assert(sizeof d == sizeof(uint32_t) * DSM_INGEST_DESC_WORDS, "descriptor words");
+  if (int rc = dsm_pcm::describe(DSM_PCM_IN, sample_rate_hz, sample_format, &d, &err)) { g_create_error = err; return rc; }
+  static_assert(sizeof d == sizeof(uint32_t) * DSM_PCM_DESC_WORDS, "descriptor words");
   memcpy(words12, &d, sizeof d);
   return 0;
 }
@@ -197,15 +134,14 @@ int dsm_asr_set_input_format(dsm_engine* e, int slot, int sample_rate_hz, int sa
   if (!e->ingest_on) { e->set_error("ingest is off: dsm_asr_set_ingest(engine, 1) comes first"); return DSM_ERR_STATE; }
   std::lock_guard<std::mutex> host(e->ingest_mu);
   uint32_t index = 0;
-  if (int rc = ingest_format_entry(e, sample_rate_hz, sample_format, &index)) return rc;
+  if (int rc = e->ingest_fmt.entry(e, sample_rate_hz, sample_format, &index)) return rc;
   // frames in flight read the slot's words: both streams drain before they change
   HIPCHK(hipStreamSynchronize(e->s_enc));
   HIPCHK(hipStreamSynchronize(e->s_model));
+  if (int rc = e->ingest_fmt.set_slot(e, slot, index)) return rc;
   const uint32_t zero = 0;
-  HIPCHK(hipMemcpy(e->ingest_slot_desc_d + slot, &index, sizeof index, hipMemcpyHostToDevice));
   for (int side = 0; side < 2; ++side) HIPCHK(hipMemcpy(e->ingest_started[side] + slot, &zero, sizeof zero, hipMemcpyHostToDevice));
   HIPCHK(hipStreamSynchronize(nullptr));
-  e->ingest_slot_desc_h[(size_t)slot] = index;
   return 0;
 }
 
@@ -214,18 +150,7 @@ int dsm_asr_input_format(dsm_engine* e, int slot, int* rate, int* fmt, int* fram
   if (slot < 0 || slot >= e->B) { e->set_error("batch index out of range: %d >= %d", slot, e->B); return DSM_ERR_INVALID; }
   ApiShared api(e);
   std::lock_guard<std::mutex> host(e->ingest_mu);
-  dsm_ingest_desc d;
-  if (e->ingest_ready) d = e->ingest_descs_h[e->ingest_slot_desc_h[(size_t)slot]];
-  else {
-    std::string err;
-    if (int rc = dsm_ingest::describe(DSM_INGEST_OUT_RATE, DSM_PCM_F32, &d, &err)) return rc;
-  }
-  if (rate) *rate = (int)d.rate;
-  if (fmt) *fmt = (int)d.fmt;
-  if (frame_samples) *frame_samples = (int)d.F_in;
-  if (frame_bytes) *frame_bytes = (int)d.frame_bytes;
-  if (latency_samples_24k) *latency_samples_24k = (int)d.D;
-  return 0;
+  return e->ingest_fmt.get(slot, rate, fmt, frame_samples, frame_bytes, latency_samples_24k);
 }
 
 int dsm_mimi_encode_step_raw(dsm_engine* e, const void* raw, size_t pitch_bytes, const uint8_t* mask, uint32_t* codes_out, int* produced) {

@@ -18,8 +18,7 @@
 #include "dsm_sampling.h"
 #include "dsm_token_scores.h"
 #include "dsm_text_bias.h"
-#include "dsm_ingest.h"
-#include "dsm_egress.h"
+#include "dsm_pcm_format.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short dsm_bf16x8 __attribute__((ext_vector_type(8)));
@@ -3142,76 +3141,81 @@ __global__ void fill_u32_kernel(uint32_t* p, uint32_t v, long n) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Ingest (dsm_ingest.h; this project's own, off by default): a slot's raw frame — its own sample rate and sample format — to the
-// 1920 samples at 24 kHz of the step, written where upload_pcm's 2-D copy writes them: MimiState::pcm at the init conv's pitch.
-// One 256-thread workgroup per slot.  The slot's history and its decoded frame are staged in dynamic LDS as f32 (at most
-// 136 + 3840 floats); each thread walks outputs n = tid, tid + 256, ... with the serial fp64 chain of dsm_ingest_output (a product
-// of two floats is exact in double: v_fma_f64 gives the host's multiply-add bits); then the frame's last `taps` samples become
-// the history.  A masked-off slot returns at once: nothing read, nothing written.  Every index is bounded by the descriptor,
-// which the engine admits through dsm_ingest::check only: LDS taps + F_in <= 3976 floats, coefficient reads inside the table.
+// Ingest and egress (dsm_pcm_format.h, which holds the definition once, with a direction; this project's own, off by default):
+// two kernels of one shape.  One 256-thread workgroup per slot; the slot's history and the step's input samples are staged in
+// dynamic LDS as f32; each thread walks outputs n = tid, tid + 256, ... with the serial fp64 chain of dsm_pcm_output (a product
+// of two floats is exact in double: v_fma_f64 gives the host's multiply-add bits); then the input's last `taps` samples become
+// the history.  A slot that is masked off, or does not emit, returns at once: nothing read, nothing written.  Every index is
+// bounded by the descriptor, which the engine admits through dsm_pcm::check only.
 // ------------------------------------------------------------------------------------------
+
+// buf[0 .. taps): the slot's history, zeros while the slot has not started
+__device__ __forceinline__ void pcm_stage_history(float* buf, const float* hist, uint32_t taps, uint32_t started, uint32_t tid) {
+  for (uint32_t i = tid; i < taps; i += 256) buf[i] = started ? hist[i] : 0.0f;
+}
+// the last `taps` of the n_in input samples behind the history become the history (LDS is read-only since the barrier)
+__device__ __forceinline__ void pcm_keep_history(float* hist, const float* buf, uint32_t n_in, uint32_t taps, uint32_t tid) {
+  for (uint32_t i = tid; i < taps; i += 256) hist[i] = buf[n_in + i];
+}
+
+// Ingest (DSM_PCM_IN): a slot's raw frame — its own sample rate and sample format — to the 1920 samples at 24 kHz of the step,
+// written where upload_pcm's 2-D copy writes them: MimiState::pcm at the init conv's pitch.  LDS: taps + frame <= 136 + 3840 =
+// 3976 floats; coefficient reads inside the table.
 struct IngestArgs {
   const uint8_t* raw;           // [B][pitch] bytes
   size_t pitch;
   const uint8_t* mask;          // [B]
   const uint32_t* slot_desc;    // [B] index into descs
-  const dsm_ingest_desc* descs;
+  const dsm_pcm_desc* descs;
   const float* coef;            // the coefficient arena
   const float* g711;            // [2][256]
-  float* hist;                  // [B][DSM_INGEST_MAX_TAPS]
+  float* hist;                  // [B][DSM_PCM_MAX_TAPS_IN]
   uint32_t* started;            // [B]
   float* pcm;                   // slot 0's frame; slots are pcm_pitch floats apart
   long pcm_pitch;
 };
 
-constexpr size_t ingest_lds() { return sizeof(float) * (DSM_INGEST_MAX_TAPS + DSM_INGEST_MAX_FRAME); }
+constexpr size_t ingest_lds() { return sizeof(float) * (DSM_PCM_MAX_TAPS_IN + DSM_PCM_MAX_FRAME); }
 __global__ __launch_bounds__(256) void ingest_resample_kernel(IngestArgs a) {
   extern __shared__ float ingest_buf[];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (!a.mask[b]) return;
-  const dsm_ingest_desc d = a.descs[a.slot_desc[b]];
+  const dsm_pcm_desc d = a.descs[a.slot_desc[b]];
   const uint8_t* row = a.raw + (size_t)b * a.pitch;
   float* out = a.pcm + (long)b * a.pcm_pitch;
-  float* hist = a.hist + (size_t)b * DSM_INGEST_MAX_TAPS;
+  float* hist = a.hist + (size_t)b * DSM_PCM_MAX_TAPS_IN;
   const uint32_t started = a.started[b];
-  for (uint32_t i = tid; i < d.taps; i += 256) ingest_buf[i] = started ? hist[i] : 0.0f;
-  for (uint32_t i = tid; i < d.F_in; i += 256) ingest_buf[d.taps + i] = dsm_unpaired(dsm_ingest_decode(d.fmt, row, i, a.g711));
+  pcm_stage_history(ingest_buf, hist, d.taps, started, tid);
+  for (uint32_t i = tid; i < d.frame; i += 256) ingest_buf[d.taps + i] = dsm_unpaired(dsm_pcm_decode(d.fmt, row, i, a.g711));
   __syncthreads();
   const float* coef = a.coef + d.table_off;
-  for (int n = tid; n < DSM_FRAME_SIZE; n += 256) out[n] = dsm_ingest_output(&d, coef, ingest_buf, started, n);
-  for (uint32_t i = tid; i < d.taps; i += 256) hist[i] = ingest_buf[d.F_in + i];  // LDS is read-only since the barrier
+  for (int n = tid; n < DSM_FRAME_SIZE; n += 256) out[n] = dsm_pcm_output(DSM_PCM_IN, &d, coef, ingest_buf, started, n);
+  pcm_keep_history(hist, ingest_buf, d.frame, d.taps, tid);
   if (tid == 0) a.started[b] = 1u;
 }
 
-// ------------------------------------------------------------------------------------------
-// Egress (dsm_egress.h; this project's own, off by default): the 1920 samples at 24 kHz a slot's decode produced — MimiDecState::pcm
-// — to a frame of the slot's own output sample rate and sample format, in the slot's row of the staging buffer the download
-// reads.  The ingest kernel run the other way, and the same shape: one 256-thread workgroup per slot; the slot's history and its
-// frame are staged in dynamic LDS as f32 (at most 204 + 1920 floats); each thread walks outputs n = tid, tid + 256, ... < F_out
-// with the serial fp64 chain of dsm_egress_output (v_fma_f64 gives the host's multiply-add bits), encodes and stores the sample
-// (a dword, a short or a byte: at most 3840 stores a row); then the frame's last `taps` samples become the history.  A slot that
-// does not emit returns at once: nothing read, nothing written.  Every index is bounded by the descriptor, which the engine
-// admits through dsm_egress::check only: LDS taps + 1920 <= 2124 floats, coefficient reads inside the table, stores inside
-// frame_bytes <= 15360 <= pitch.
-// ------------------------------------------------------------------------------------------
+// Egress (DSM_PCM_OUT): the 1920 samples at 24 kHz a slot's decode produced — MimiDecState::pcm — to a frame of the slot's own
+// output sample rate and sample format, in the slot's row of the staging buffer the download reads.  Outputs n < frame, each
+// encoded and stored (a dword, a short or a byte: at most 3840 stores a row).  LDS: taps + 1920 <= 204 + 1920 = 2124 floats;
+// coefficient reads inside the table, stores inside frame_bytes <= 15360 <= pitch.
 struct EgressArgs {
   const float* pcm;             // [B][DSM_FRAME_SIZE] the decoder's frames
   const uint8_t* valid;         // [B] the decoder's mask: the slot emits
   const uint32_t* slot_desc;    // [B] index into descs
-  const dsm_egress_desc* descs;
+  const dsm_pcm_desc* descs;
   const float* coef;            // the coefficient arena
-  float* hist;                  // [B][DSM_EGRESS_MAX_TAPS]
+  float* hist;                  // [B][DSM_PCM_MAX_TAPS_OUT]
   uint32_t* started;            // [B]
   uint8_t* raw;                 // [B][pitch] bytes, rows 16-byte aligned
   size_t pitch;
 };
 
-constexpr size_t egress_lds() { return sizeof(float) * (DSM_EGRESS_MAX_TAPS + DSM_FRAME_SIZE); }
+constexpr size_t egress_lds() { return sizeof(float) * (DSM_PCM_MAX_TAPS_OUT + DSM_FRAME_SIZE); }
 __global__ __launch_bounds__(256) void egress_resample_kernel(EgressArgs a) {
   extern __shared__ float egress_buf[];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (!a.valid[b]) return;
-  const dsm_egress_desc d = a.descs[a.slot_desc[b]];
+  const dsm_pcm_desc d = a.descs[a.slot_desc[b]];
   const float* frame = a.pcm + (size_t)b * DSM_FRAME_SIZE;
   uint8_t* row = (uint8_t*)__builtin_assume_aligned(a.raw + (size_t)b * a.pitch, 16);
   if (d.taps == 0u && d.fmt == DSM_PCM_F32) {  // pass-through: the bits as they are, no state but "started"
@@ -3221,13 +3225,14 @@ __global__ __launch_bounds__(256) void egress_resample_kernel(EgressArgs a) {
     if (tid == 0) a.started[b] = 1u;
     return;
   }
-  float* hist = a.hist + (size_t)b * DSM_EGRESS_MAX_TAPS;
+  float* hist = a.hist + (size_t)b * DSM_PCM_MAX_TAPS_OUT;
   const uint32_t started = a.started[b];
-  for (uint32_t i = tid; i < d.taps; i += 256) egress_buf[i] = started ? hist[i] : 0.0f;
+  pcm_stage_history(egress_buf, hist, d.taps, started, tid);
   for (uint32_t i = tid; i < DSM_FRAME_SIZE; i += 256) egress_buf[d.taps + i] = frame[i];
   __syncthreads();
   const float* coef = a.coef + d.table_off;
-  for (uint32_t n = tid; n < d.F_out; n += 256) dsm_egress_store(d.fmt, row, n, dsm_unpaired(dsm_egress_output(&d, coef, egress_buf, started, (int)n)));
-  for (uint32_t i = tid; i < d.taps; i += 256) hist[i] = egress_buf[DSM_FRAME_SIZE + i];  // LDS is read-only since the barrier
+  for (uint32_t n = tid; n < d.frame; n += 256)
+    dsm_pcm_store(d.fmt, row, n, dsm_unpaired(dsm_pcm_output(DSM_PCM_OUT, &d, coef, egress_buf, started, (int)n)));
+  pcm_keep_history(hist, egress_buf, DSM_FRAME_SIZE, d.taps, tid);
   if (tid == 0) a.started[b] = 1u;
 }

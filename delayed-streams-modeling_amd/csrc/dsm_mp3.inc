@@ -13,7 +13,7 @@
 // Not built: MPEG-2 / 2.5 (LSF) streams, Layers I / II, free-format bit rates, CRC verification (the check word is skipped).
 // Intensity stereo follows the standard's text but no sample exercises it (all five files are mono).
 #include <math.h>
-#include "dsm_ingest.h"  // guarded: the phase table of the resampler, shared with the per-slot ingest
+#include "dsm_pcm_format.h"  // guarded: the phase table of the resampler, shared with the per-slot ingest and egress
 
 namespace dsm_mp3 {
 
@@ -550,7 +550,7 @@ static int decode_stream(const uint8_t* b, size_t len, std::vector<float>* left,
 // cut-off at 0.5 min(rate_in, rate_out) x 0.95.  kaudio is an un-vendored crate (it wraps a sinc resampler of the same family);
 // its coefficients are not reproduced — parity unpinned, the properties are tested (DC gain, a tone keeps its frequency and
 // level, images below -80 dB).
-// The phase table (Kaiser beta 8.6, per-phase normalisation, stored as float) is dsm_ingest::phase_table (dsm_ingest.h), shared
+// The phase table (Kaiser beta 8.6, per-phase normalisation, stored as float) is dsm_pcm::phase_table (dsm_pcm_format.h), shared
 // with the streaming per-slot ingest, whose definition is this function's output cut into frames.
 static int resample(const float* in, size_t n, int rin, int rout, std::vector<float>* out) {
   if (rin <= 0 || rout <= 0) return -1;
@@ -558,7 +558,7 @@ static int resample(const float* in, size_t n, int rin, int rout, std::vector<fl
   long L = 0, M = 0;
   int half = 0;
   std::vector<float> ph;
-  if (dsm_ingest::phase_table(rin, rout, &L, &M, &half, &ph)) return -1;
+  if (dsm_pcm::phase_table(rin, rout, &L, &M, &half, &ph)) return -1;
   const int taps = 2 * half;
   const size_t nout = (size_t)(((unsigned long long)n * (unsigned long long)L + M - 1) / M);
   out->resize(nout);

@@ -139,7 +139,7 @@ struct dsm_tts : DsmDevice {
     uint8_t* h_valid = nullptr; // [B]
     bool launched = false;      // false: no slot could emit, nothing was enqueued, valid is all zero
     // egress (dsm_egress.inc): with the section on the entry receives raw rows in the place of h_pcm
-    uint8_t* h_raw = nullptr;   // [B][DSM_EGRESS_MAX_FRAME_BYTES] pinned, allocated by the first dsm_tts_set_egress(1)
+    uint8_t* h_raw = nullptr;   // [B][DSM_PCM_MAX_FRAME_BYTES] pinned, allocated by the first dsm_tts_set_egress(1)
     size_t raw_pitch = 0;       // the pitch the rows of this entry were written and downloaded at
     std::vector<uint32_t> fb;   // [B] every slot's frame_bytes when the entry was enqueued
   };
@@ -176,21 +176,18 @@ struct dsm_tts : DsmDevice {
   PcmEntry blk_pcm[DSM_TTS_RUN_MAX];
   int blk_pending = 0;    // steps of the block that waits for dsm_tts_collect (0: none)
   bool blk_decode = false;
-  // ---- egress (dsm_tts_set_egress; dsm_egress.h, dsm_egress.inc): a sample rate and a sample format per slot ----
-  // What egress_resample_kernel reads: the format descriptors [kEgressFormats] (entry 0 = 24000 / F32, append-only: one per
-  // (rate, format) ever set), the coefficient arena (append-only: one phase table per rate), each slot's descriptor index [B],
-  // the history [B][204] and the "started" words [B]; what it writes: the staging rows [B][15360], at egress_pitch — the largest
-  // frame_bytes of any slot, rounded up to 16 — which is also what a step downloads.  All of it allocated by the first
-  // dsm_tts_set_egress(1), with a pinned raw buffer beside every PcmEntry.  Host side: mirrors of the descriptors and indices.
-  static constexpr size_t kEgressFormats = 64, kEgressCoefWords = (size_t)1 << 20;
-  bool egress_on = false, egress_ready = false;
-  dsm_egress_desc* egress_descs_d = nullptr;
-  float *egress_coef_d = nullptr, *egress_hist = nullptr, *egress_dbg_pcm = nullptr;
-  uint32_t *egress_slot_desc_d = nullptr, *egress_started = nullptr;
+  // ---- egress (dsm_tts_set_egress; dsm_pcm_format.h, dsm_egress.inc): a sample rate and a sample format per slot ----
+  // What egress_resample_kernel reads: the slots' formats (PcmFormatTable, dsm_pcm_table.inc: descriptors, coefficient arena, each
+  // slot's descriptor index, with their host mirrors), the history [B][204] and the "started" words [B]; what it writes: the
+  // staging rows [B][15360], at egress_pitch — the largest frame_bytes of any slot, rounded up to 16 — which is also what a step
+  // downloads.  All of it allocated by the first dsm_tts_set_egress(1), with a pinned raw buffer beside every PcmEntry, after
+  // which egress_fmt.ready holds.
+  bool egress_on = false;
+  PcmFormatTable egress_fmt{DSM_PCM_OUT};
+  float *egress_hist = nullptr, *egress_dbg_pcm = nullptr;
+  uint32_t* egress_started = nullptr;
   uint8_t *egress_raw_d = nullptr, *egress_dbg_valid = nullptr;
-  std::vector<dsm_egress_desc> egress_descs_h;
-  std::vector<uint32_t> egress_slot_desc_h;
-  size_t egress_coef_used = 0, egress_pitch = sizeof(float) * DSM_FRAME_SIZE;
+  size_t egress_pitch = sizeof(float) * DSM_FRAME_SIZE;
 };
 
 namespace {
@@ -1126,7 +1123,7 @@ int dsm_tts_reset_slot(dsm_tts* t, int slot) {
     // The slot's next generation decodes with a fresh Mimi (srv/tts.rs:499-500: clone() + reset_state()): conv states and carries
     // zero, not started, and — unlike Mimi::reset_batch_idx — the decoder transformer back at position 0.  On the decode stream,
     // i.e. behind the decodes already queued for the old generation.  Egress: the slot's history goes with it, its format stays.
-    if (t->egress_ready) HIPCHK(hipMemsetAsync(t->egress_started + slot, 0, sizeof(uint32_t), e->s_enc));
+    if (t->egress_fmt.ready) HIPCHK(hipMemsetAsync(t->egress_started + slot, 0, sizeof(uint32_t), e->s_enc));
     return reset_decoder_slot(e, t->mimi_w, t->dec, e->s_enc, slot, true);
   }
   return 0;

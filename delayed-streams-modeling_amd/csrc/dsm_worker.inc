@@ -493,14 +493,14 @@ int dsm_worker_set_input_rate(dsm_worker* w, int slot, int hz) {
   // samples already queued or cut were counted in frames of the old rate
   if (!c.data.empty() || c.steps) { w->err = "the input rate is set before the channel's first audio is cut into frames"; return DSM_ERR_STATE; }
 #ifndef DSM_HOST_ONLY
-  dsm_ingest_desc d;
+  dsm_pcm_desc d;
   std::string derr;
-  if (int rc = dsm_ingest::describe(hz, DSM_PCM_F32, &d, &derr)) { w->err = derr; return rc; }
+  if (int rc = dsm_pcm::describe(DSM_PCM_IN, hz, DSM_PCM_F32, &d, &derr)) { w->err = derr; return rc; }
   if (int rc = dsm_asr_set_ingest(w->eng, 1)) { w->err = dsm_last_error(w->eng); return rc; }  // a no-op once it is on
   if (int rc = dsm_asr_set_input_format(w->eng, slot, hz, DSM_PCM_F32)) { w->err = dsm_last_error(w->eng); return rc; }
-  if (w->batch_raw.empty()) w->batch_raw.assign((size_t)w->B * DSM_INGEST_MAX_FRAME, 0.0f);
+  if (w->batch_raw.empty()) w->batch_raw.assign((size_t)w->B * DSM_PCM_MAX_FRAME, 0.0f);
   c.rate = hz;
-  c.frame = d.F_in;
+  c.frame = d.frame;
 #endif
   return 0;
 }

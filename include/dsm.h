@@ -1023,7 +1023,7 @@ int dsm_worker_set_bias(dsm_worker*, int slot, int set);
 
 /* ---- ingest: per-stream input sample rate and sample format, resampled on the device (this project's own: the reference
  * resamples request bodies only, srv/batched_asr.rs:835-838, and its sockets must send 24 kHz f32).  Off by default: nothing is
- * allocated and every other call enqueues exactly what it enqueues without this section.  Definition (csrc/dsm_ingest.h,
+ * allocated and every other call enqueues exactly what it enqueues without this section.  Definition (csrc/dsm_pcm_format.h,
  * bit-identical on host and device): a slot's FORMAT is a sample rate — 8000 .. 48000 Hz with a whole number F_in = 2 rate / 25
  * of samples per 80 ms frame (8000, 11025, 16000, 22050, 32000, 44100, 48000 among them) — and a sample format: DSM_PCM_F32,
  * DSM_PCM_S16 (little endian, v / 32768), DSM_PCM_MULAW, DSM_PCM_ALAW (ITU-T G.711, expanded to 16 bits, then as s16).  With x
@@ -1087,7 +1087,7 @@ int dsm_worker_set_input_rate(dsm_worker*, int slot, int hz);
 /* ---- egress: per-slot TTS output sample rate and sample format, resampled and encoded on the device (this project's own: the
  * reference's TTS sockets send 24 kHz f32, srv/tts.rs:528-544).  The ingest section run the other way — the same rates, the same
  * DSM_PCM_* formats, the same filter family.  Off by default: nothing is allocated and every other call enqueues exactly what it
- * enqueues without this section.  Definition (csrc/dsm_egress.h, bit-identical on host and device): a slot's FORMAT is a sample
+ * enqueues without this section.  Definition (csrc/dsm_pcm_format.h, bit-identical on host and device): a slot's FORMAT is a sample
  * rate — 8000 .. 48000 Hz with a whole number F_out = 2 rate / 25 of samples per 80 ms frame — and a sample format:
  * DSM_PCM_F32, DSM_PCM_S16 (little endian, rint(v 32768) clamped, NaN 0), DSM_PCM_MULAW, DSM_PCM_ALAW (ITU-T G.711 of that
  * 16-bit value).  With x the slot's emitted PCM since the format was set (only the frames whose valid flag is 1) and

@@ -1,4 +1,4 @@
-"""Python restatement of the egress definition, written from the definition and not from csrc/dsm_egress.h: the frame and
+"""Python restatement of the egress definition, written from the definition and not from csrc/dsm_pcm_format.h: the frame and
 filter geometry of an output rate, the whole-clip resampler's indexing with the brute-force search for the latency D and for the
 history a step reads, the three sample encoders, and the streaming cut of a whole-clip result.  The filter coefficients are not
 restated: the definition names the whole-clip function dsm_resample(x, 24000, rate) as the signal, and the tests compare with it."""

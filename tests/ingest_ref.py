@@ -1,4 +1,4 @@
-"""Python restatement of the ingest definition (csrc/dsm_ingest.h), written from the definition and not from the code: the G.711
+"""Python restatement of the ingest definition (csrc/dsm_pcm_format.h), written from the definition and not from the code: the G.711
 expansions by the ITU-T formulas, the frame and latency arithmetic with its brute-force counterparts, the decoding of a raw
 frame, and the streaming cut of a whole-clip result.  The filter itself is not restated: the definition names the whole-clip
 function dsm_resample as the signal, and the tests compare against it."""

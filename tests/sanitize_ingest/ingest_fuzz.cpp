@@ -1,12 +1,13 @@
-// ingest_fuzz — the host code of the ingest section (csrc/dsm_ingest.h: the descriptor of a format, its checked reader, the
+// ingest_fuzz — the host code of the ingest section (csrc/dsm_pcm_format.h, DSM_PCM_IN: the descriptor of a format, its checked reader, the
 // streaming host function) under AddressSanitizer + UBSan.  A stand-alone program with its own main:
 //   1  every supported common rate x every sample format streams seeded frames, each copied into a heap buffer of exactly the
-//      format's frame length (so a read past the frame is a report), through host_step; the outputs are finite for finite input;
+//      format's frame length (so a read past the frame is a report), through host_step_in; the outputs are finite for finite input;
 //   2  random rates and formats, valid and not, go through describe() and host_new(): accepted or refused with a message; what
 //      is accepted passes check() and streams two frames;
 //   3  valid descriptors mutated (one word overwritten with an edge value), and wholly random ones, go through check() with
 //      random arena lengths: a clean 0 or a clean DSM_ERR_INVALID; a mutated descriptor put into a live state, and frames
-//      shorter or longer than declared, are refused by host_step before anything is read.
+//      shorter or longer than declared, are refused by host_step_in before anything is read; a resampling descriptor made for
+//      the other direction is refused by check().
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -16,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "../../delayed-streams-modeling_amd/csrc/dsm_ingest.h"
+#include "../../delayed-streams-modeling_amd/csrc/dsm_pcm_format.h"
 
 static uint64_t rng_state = 0x1A6E57ull;
 static uint64_t rnd() {  // splitmix64
@@ -53,12 +54,12 @@ static std::unique_ptr<uint8_t[]> frame_of(uint32_t fmt, size_t bytes) {
   return p;
 }
 
-static int stream(dsm_ingest::Host* h, int frames) {
+static int stream(dsm_pcm::Host* h, int frames) {
   std::string err;
   std::vector<float> out(DSM_FRAME_SIZE);
   for (int t = 0; t < frames; ++t) {
     auto f = frame_of(h->d.fmt, h->d.frame_bytes);
-    CHECK(dsm_ingest::host_step(h, f.get(), h->d.frame_bytes, out.data(), &err) == 0);
+    CHECK(dsm_pcm::host_step_in(h, f.get(), h->d.frame_bytes, out.data(), &err) == 0);
     for (float v : out) CHECK(std::isfinite(v) && std::fabs(v) < 4.0f);
   }
   return 0;
@@ -70,10 +71,10 @@ int main() {
   // 1
   for (int rate : rates)
     for (int fmt = 0; fmt < 4; ++fmt) {
-      dsm_ingest::Host h;
-      CHECK(dsm_ingest::host_new(rate, fmt, &h, &err) == 0);
-      CHECK(h.d.F_in * 25u == 2u * (uint32_t)rate && h.d.taps <= DSM_INGEST_MAX_TAPS && h.d.F_in <= DSM_INGEST_MAX_FRAME);
-      CHECK(h.d.frame_bytes <= DSM_INGEST_MAX_FRAME_BYTES && h.coef.size() == h.d.table_words);
+      dsm_pcm::Host h;
+      CHECK(dsm_pcm::host_new(DSM_PCM_IN, rate, fmt, &h, &err) == 0);
+      CHECK(h.d.frame * 25u == 2u * (uint32_t)rate && h.d.taps <= DSM_PCM_MAX_TAPS_IN && h.d.frame <= DSM_PCM_MAX_FRAME);
+      CHECK(h.d.frame_bytes <= DSM_PCM_MAX_FRAME_BYTES && h.coef.size() == h.d.table_words);
       if (stream(&h, 3)) return 1;
       // frames shorter and longer than declared: refused, the state as it was
       const std::vector<float> before = h.buf;
@@ -81,10 +82,12 @@ int main() {
       for (size_t bytes : {(size_t)0, (size_t)1, (size_t)h.d.frame_bytes - 1, (size_t)h.d.frame_bytes + 1, (size_t)below(h.d.frame_bytes)}) {
         auto f = frame_of((uint32_t)fmt, bytes);
         err.clear();
-        CHECK(dsm_ingest::host_step(&h, f.get(), bytes, out.data(), &err) == DSM_ERR_INVALID && !err.empty());
+        CHECK(dsm_pcm::host_step_in(&h, f.get(), bytes, out.data(), &err) == DSM_ERR_INVALID && !err.empty());
       }
       CHECK(h.buf == before);
-      CHECK(dsm_ingest::host_step(&h, nullptr, h.d.frame_bytes, out.data(), &err) == DSM_ERR_INVALID);
+      CHECK(dsm_pcm::host_step_in(&h, nullptr, h.d.frame_bytes, out.data(), &err) == DSM_ERR_INVALID);
+      // the direction is no word of the descriptor: where the two differ (every rate that resamples) check() tells them apart
+      CHECK(dsm_pcm::check(DSM_PCM_OUT, &h.d, h.coef.size(), &err) == (rate == DSM_PCM_RATE ? 0 : DSM_ERR_INVALID));
       if (stream(&h, 1)) return 1;
     }
   // 2
@@ -98,53 +101,53 @@ int main() {
       default: rate = -(long)below(50000); break;
     }
     fmt = below(3) ? (long)below(4) : (long)(int32_t)kEdgeWords[below(sizeof kEdgeWords / sizeof *kEdgeWords)];
-    dsm_ingest_desc d;
+    dsm_pcm_desc d;
     err.clear();
-    const int rc = dsm_ingest::describe(rate, fmt, &d, &err);
-    dsm_ingest::Host h;
+    const int rc = dsm_pcm::describe(DSM_PCM_IN, rate, fmt, &d, &err);
+    dsm_pcm::Host h;
     std::string err2;
-    const int rc2 = dsm_ingest::host_new(rate, fmt, &h, &err2);
+    const int rc2 = dsm_pcm::host_new(DSM_PCM_IN, rate, fmt, &h, &err2);
     CHECK(rc == rc2);
     if (rc) { CHECK(rc == DSM_ERR_INVALID && !err.empty() && !err2.empty()); continue; }
     CHECK(rate >= 8000 && rate <= 48000 && rate % 25 == 0 && fmt >= 0 && fmt < 4);
-    CHECK(dsm_ingest::check(&h.d, h.coef.size(), &err) == 0);
+    CHECK(dsm_pcm::check(DSM_PCM_IN, &h.d, h.coef.size(), &err) == 0);
     if (accepted++ < 40 && stream(&h, 2)) return 1;  // the phase table of an odd rate has up to 960 phases: a few dozen are enough
   }
   CHECK(accepted > 50);
   // 3
   for (int it = 0; it < 4000; ++it) {
-    dsm_ingest_desc d;
-    uint32_t w[DSM_INGEST_DESC_WORDS];
+    dsm_pcm_desc d;
+    uint32_t w[DSM_PCM_DESC_WORDS];
     const bool mutated = below(3) != 0;
     if (mutated) {
-      CHECK(dsm_ingest::describe(rates[below(8)], (long)below(4), &d, &err) == 0);
+      CHECK(dsm_pcm::describe(DSM_PCM_IN, rates[below(8)], (long)below(4), &d, &err) == 0);
       memcpy(w, &d, sizeof w);
-      const uint32_t at = below(DSM_INGEST_DESC_WORDS);
+      const uint32_t at = below(DSM_PCM_DESC_WORDS);
       w[at] = below(2) ? kEdgeWords[below(sizeof kEdgeWords / sizeof *kEdgeWords)] : w[at] + 1u - 2u * below(2);
     } else {
       for (uint32_t& x : w) x = below(2) ? (uint32_t)rnd() : kEdgeWords[below(sizeof kEdgeWords / sizeof *kEdgeWords)];
     }
-    std::unique_ptr<dsm_ingest_desc> heap(new dsm_ingest_desc);
+    std::unique_ptr<dsm_pcm_desc> heap(new dsm_pcm_desc);
     memcpy(heap.get(), w, sizeof w);
     const size_t arena = below(2) ? (size_t)below(200000) : (size_t)heap->table_off + heap->table_words - below(2);
     err.clear();
-    const int rc = dsm_ingest::check(heap.get(), arena, &err);
+    const int rc = dsm_pcm::check(DSM_PCM_IN, heap.get(), arena, &err);
     CHECK(rc == 0 || (rc == DSM_ERR_INVALID && !err.empty()));
     if (rc == 0) {  // then every index of a step is inside the frame, the history and the arena
-      CHECK(heap->taps <= DSM_INGEST_MAX_TAPS && heap->F_in <= DSM_INGEST_MAX_FRAME && heap->taps == 2u * heap->half);
+      CHECK(heap->taps <= DSM_PCM_MAX_TAPS_IN && heap->frame <= DSM_PCM_MAX_FRAME && heap->taps == 2u * heap->half);
       CHECK((uint64_t)heap->table_off + (uint64_t)heap->L * heap->taps <= arena && heap->reserved == 0u);
-      CHECK(heap->frame_bytes == heap->F_in * dsm_ingest_sample_bytes(heap->fmt));
+      CHECK(heap->frame_bytes == heap->frame * dsm_pcm_sample_bytes(heap->fmt));
     }
     if (mutated && it % 8 == 0) {  // the mutated descriptor inside a live state: host_step checks before it reads
-      dsm_ingest::Host h;
-      CHECK(dsm_ingest::host_new(rates[below(8)], (long)below(4), &h, &err) == 0);
-      const dsm_ingest_desc good = h.d;
+      dsm_pcm::Host h;
+      CHECK(dsm_pcm::host_new(DSM_PCM_IN, rates[below(8)], (long)below(4), &h, &err) == 0);
+      const dsm_pcm_desc good = h.d;
       h.d = *heap;
       std::vector<float> out(DSM_FRAME_SIZE);
       auto f = frame_of(good.fmt, good.frame_bytes);
-      const int rs = dsm_ingest::host_step(&h, f.get(), good.frame_bytes, out.data(), &err);
+      const int rs = dsm_pcm::host_step_in(&h, f.get(), good.frame_bytes, out.data(), &err);
       CHECK(rs == 0 || rs == DSM_ERR_INVALID);
-      if (rs == 0) CHECK(h.d.frame_bytes == good.frame_bytes && h.buf.size() == (size_t)h.d.taps + h.d.F_in);
+      if (rs == 0) CHECK(h.d.frame_bytes == good.frame_bytes && h.buf.size() == (size_t)h.d.taps + h.d.frame);
     }
   }
   puts("ingest_fuzz ok");

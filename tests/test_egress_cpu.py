@@ -1,4 +1,4 @@
-"""Egress on the host (csrc/dsm_egress.h; no GPU): every descriptor word is the restatement's (tests/egress_ref.py) and the
+"""Egress on the host (csrc/dsm_pcm_format.h; no GPU): every descriptor word is the restatement's (tests/egress_ref.py) and the
 definition's table; D is the brute-force minimum and the kept history covers the brute-force reach; what is outside the
 definition is refused; dsm_egress_host, streamed frame by frame as F32, delivers the whole-clip resampler's output delayed by D,
 bit for bit, for every rate; the sample encoders over all 65536 16-bit values against the restatement and the standard library's

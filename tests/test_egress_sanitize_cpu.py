@@ -1,4 +1,4 @@
-"""The egress section's host code (csrc/dsm_egress.h: the descriptor of an output format, its checked reader, the sample
+"""The egress section's host code (csrc/dsm_pcm_format.h: the descriptor of an output format, its checked reader, the sample
 encoders, the streaming host function) under AddressSanitizer + UBSan: a stand-alone program (tests/sanitize_egress/egress_fuzz.cpp,
 its own main, nothing preloaded, no Python inside) streams every admitted rate and format into heap rows of exactly the declared
 length with extreme sample values among the input, mutates every descriptor word — each is refused — moves table offsets to and

@@ -1,4 +1,4 @@
-"""Ingest on the host (csrc/dsm_ingest.h; no GPU): dsm_ingest_host, streamed frame by frame, delivers the whole-clip resampler's
+"""Ingest on the host (csrc/dsm_pcm_format.h; no GPU): dsm_ingest_host, streamed frame by frame, delivers the whole-clip resampler's
 output delayed by the format's latency D, bit for bit, for every supported rate and sample format, extremes and the start of the
 stream included; D is the brute-force minimum and the kept history covers the brute-force reach; the G.711 tables are the
 standard library's; the pass-through format returns its input bytes; what is outside the definition is refused with a message;

@@ -1,4 +1,4 @@
-"""Ingest on the GPU (dsm_asr_set_ingest; csrc/dsm_ingest.h): ingest_resample_kernel hands Mimi the frames of the host function
+"""Ingest on the GPU (dsm_asr_set_ingest; csrc/dsm_pcm_format.h): ingest_resample_kernel hands Mimi the frames of the host function
 dsm_ingest_host, bit for bit, per slot and step — four slots with four formats, a masked stretch, a format switched in
 mid-stream —, and everything downstream (codes, text tokens, VAD values, messages) is what a plain engine computes from the host
 function's 24 kHz frames, through the synchronous, the ticket, the device-pointer and the model-side entry points; the

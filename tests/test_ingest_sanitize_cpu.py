@@ -1,4 +1,4 @@
-"""The ingest section's host code (csrc/dsm_ingest.h: the descriptor of an input format, its checked reader, the streaming host
+"""The ingest section's host code (csrc/dsm_pcm_format.h: the descriptor of an input format, its checked reader, the streaming host
 function) under AddressSanitizer + UBSan: a stand-alone program (tests/sanitize_ingest/ingest_fuzz.cpp, its own main, nothing
 preloaded, no Python inside) streams every common rate and format from heap frames of exactly the declared length, feeds random
 rates and formats, random and mutated descriptors and frames shorter than declared — each is accepted or refused cleanly."""
