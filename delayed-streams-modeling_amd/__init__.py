@@ -170,6 +170,9 @@ ABI_SYMBOLS = [
     "dsm_tts_set_egress", "dsm_tts_set_output_format", "dsm_tts_output_format", "dsm_tts_step_raw", "dsm_tts_recv_raw",
     "dsm_tts_collect_raw", "dsm_tts_debug_egress", "dsm_egress_host_new", "dsm_egress_host_free", "dsm_egress_host",
     "dsm_egress_describe", "dsm_egress_encode_sample",
+    "dsm_asr_set_clips", "dsm_asr_clip_begin", "dsm_asr_clip_push", "dsm_asr_clip_close", "dsm_asr_run", "dsm_asr_collect",
+    "dsm_asr_clip_status", "dsm_asr_clip_frame_host", "dsm_asr_clip_host_new", "dsm_asr_clip_host_free", "dsm_asr_clip_host_begin",
+    "dsm_asr_clip_host_push", "dsm_asr_clip_host_close", "dsm_asr_clip_host_reset", "dsm_asr_clip_host_status", "dsm_asr_clip_host_run",
 ]
 PCM_F32, PCM_S16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3  # DSM_PCM_*: the sample formats of the ingest and egress sections
 INGEST_MAX_FRAME_BYTES = 15360  # the largest raw frame (48 kHz f32) and the largest pitch of the raw calls
@@ -236,6 +239,19 @@ class TtsConditionerDesc(C.Structure):
                 ("scale_factor", C.c_float), ("max_period", C.c_float)]
 
 
+ASR_RUN_MAX = 16  # DSM_ASR_RUN_MAX
+ASR_CLIP_IDLE, ASR_CLIP_RUNNING, ASR_CLIP_WAITING, ASR_CLIP_DONE = range(4)  # DSM_ASR_CLIP_*
+
+
+class AsrBlockC(C.Structure):
+    """dsm_asr_block (include/dsm.h): caller-provided arrays of one dsm_asr_run block."""
+    _fields_ = [("n_steps", C.c_int), ("stepped", C.c_void_p), ("text_token", C.c_void_p), ("vad_prs", C.c_void_p),
+                ("logprob", C.c_void_p), ("msgs", C.POINTER(AsrMsg)), ("msg_step", C.POINTER(C.c_int)), ("msgs_cap", C.c_int),
+                ("n_msgs", C.c_int), ("msg_tokens", C.c_void_p), ("msg_logprobs", C.c_void_p), ("tokens_cap", C.c_int),
+                ("n_tokens", C.c_int), ("status", C.c_void_p)]
+
+
+AsrBlock = collections.namedtuple("AsrBlock", "n_steps stepped text_token vad_prs logprob msgs word_scores status")
 TtsBlock = collections.namedtuple("TtsBlock", "n_steps stepped text_token audio pcm pcm_valid events status")
 PROF_TAGS = ["attn_lm", "gemm_lm", "attn_mimi", "gemm_mimi", "rvq", "other"]
 
@@ -476,6 +492,27 @@ def load_library(path=None):
     for name in ("dsm_asr_set_ingest", "dsm_asr_set_input_format", "dsm_asr_input_format", "dsm_mimi_encode_step_raw",
                  "dsm_mimi_encode_step_raw_async", "dsm_mimi_encode_step_raw_dev", "dsm_asr_step_raw", "dsm_debug_ingest_read",
                  "dsm_ingest_host", "dsm_ingest_describe", "dsm_ingest_g711_table", "dsm_worker_set_input_rate"):
+        getattr(lib, name).restype = C.c_int
+    lib.dsm_asr_set_clips.argtypes = [vp, C.c_int, C.c_size_t]
+    lib.dsm_asr_clip_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.dsm_asr_clip_push.argtypes = [vp, C.c_int, vp, C.c_size_t]
+    lib.dsm_asr_clip_close.argtypes = [vp, C.c_int]
+    lib.dsm_asr_run.argtypes = [vp, C.c_int]
+    lib.dsm_asr_collect.argtypes = [vp, C.POINTER(AsrBlockC)]
+    lib.dsm_asr_clip_status.argtypes = [vp, C.c_int]
+    lib.dsm_asr_clip_frame_host.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_uint64, vp]
+    lib.dsm_asr_clip_host_new.argtypes = [C.c_int, C.c_size_t]
+    lib.dsm_asr_clip_host_new.restype = C.c_void_p
+    lib.dsm_asr_clip_host_free.argtypes = [vp]
+    lib.dsm_asr_clip_host_free.restype = None
+    lib.dsm_asr_clip_host_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.dsm_asr_clip_host_push.argtypes = [vp, C.c_int, C.c_size_t]
+    for name in ("dsm_asr_clip_host_close", "dsm_asr_clip_host_reset", "dsm_asr_clip_host_status"):
+        getattr(lib, name).argtypes = [vp, C.c_int]
+    lib.dsm_asr_clip_host_run.argtypes = [vp, C.c_int, vp, vp]
+    for name in ("dsm_asr_set_clips", "dsm_asr_clip_begin", "dsm_asr_clip_push", "dsm_asr_clip_close", "dsm_asr_run", "dsm_asr_collect",
+                 "dsm_asr_clip_status", "dsm_asr_clip_frame_host", "dsm_asr_clip_host_begin", "dsm_asr_clip_host_push",
+                 "dsm_asr_clip_host_close", "dsm_asr_clip_host_reset", "dsm_asr_clip_host_status", "dsm_asr_clip_host_run"):
         getattr(lib, name).restype = C.c_int
     lib.dsm_tts_set_egress.argtypes = [vp, C.c_int]
     lib.dsm_tts_set_output_format.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -1161,6 +1198,67 @@ class egress_host(_pcm_host):
         return self._step(_ptr(frame), np.zeros(self.frame_bytes, dtype=np.uint8))
 
 
+def asr_clip_frame_host(clip, rate, fmt, index):
+    """dsm_asr_clip_frame_host: frame `index` of a clip (bytes in the format (rate, fmt)) as bytes — the clip's bytes
+    [index * frame_bytes, (index + 1) * frame_bytes) followed by the format's silence byte (csrc/dsm_asr_clip.h)."""
+    clip = bytes(clip)
+    out = np.zeros(INGEST_MAX_FRAME_BYTES, dtype=np.uint8)
+    src = np.frombuffer(clip, dtype=np.uint8) if clip else None
+    n = load_library().dsm_asr_clip_frame_host(_ptr(src), len(clip), int(rate), int(fmt), int(index), _ptr(out))
+    if n < 0:
+        msg = load_library().dsm_last_error(None)
+        raise DsmError(f"dsm_asr_clip_frame_host: {msg.decode() if msg else '?'}")
+    return out[:n].tobytes()
+
+
+class asr_clip_host:
+    """dsm_asr_clip_host_*: the schedule dsm_asr_run goes through, on the host alone — B slots, a cap per clip; begin / push (a
+    byte count) / close / reset / status as the engine's, run(n) -> (frame [n][B] u32, mask [n][B] u8)."""
+
+    def __init__(self, B, max_clip_bytes):
+        self.lib, self.B = load_library(), int(B)
+        self.h = self.lib.dsm_asr_clip_host_new(self.B, int(max_clip_bytes))
+        if not self.h:
+            raise DsmError("dsm_asr_clip_host_new: a batch size below 1 or a cap outside 1 .. 2^31")
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise DsmError(f"dsm_asr_clip_host_{what}: error {rc}")
+        return rc
+
+    def begin(self, slot, rate, fmt, flush_frames):
+        self._check(self.lib.dsm_asr_clip_host_begin(self.h, int(slot), int(rate), int(fmt), int(flush_frames)), "begin")
+
+    def push(self, slot, n):
+        self._check(self.lib.dsm_asr_clip_host_push(self.h, int(slot), int(n)), "push")
+
+    def close(self, slot):
+        self._check(self.lib.dsm_asr_clip_host_close(self.h, int(slot)), "close")
+
+    def reset(self, slot):
+        self._check(self.lib.dsm_asr_clip_host_reset(self.h, int(slot)), "reset")
+
+    def status(self, slot):
+        return self._check(self.lib.dsm_asr_clip_host_status(self.h, int(slot)), "status")
+
+    def run(self, n_steps):
+        n = int(n_steps)
+        frame, mask = np.zeros((max(n, 1), self.B), dtype=np.uint32), np.zeros((max(n, 1), self.B), dtype=np.uint8)
+        self._check(self.lib.dsm_asr_clip_host_run(self.h, n, _ptr(frame), _ptr(mask)), "run")
+        return frame, mask
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.lib.dsm_asr_clip_host_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class LinearResampler:
     """kyutai-client-core `LinearResampler` (audio.rs:133-183) behind the C ABI; process() is streaming."""
 
@@ -1504,6 +1602,63 @@ class AsrEngine:
         out = np.zeros((self.B, FRAME_SIZE), dtype=np.float32)
         self._check(self.lib.dsm_debug_ingest_read(self.h, int(side), _ptr(out)))
         return out
+
+    # clips (include/dsm.h "clips"): a slot's audio resident on the device in its own format, K steps per visit
+    def set_clips(self, on, max_clip_bytes=0):
+        """dsm_asr_set_clips: the engine-wide switch; on allocates [B][max_clip_bytes] for the clips and turns ingest on."""
+        self._check(self.lib.dsm_asr_set_clips(self.h, 1 if on else 0, int(max_clip_bytes)))
+
+    def clip_begin(self, slot, rate, fmt=PCM_F32, flush_frames=0):
+        """dsm_asr_clip_begin: the slot is reset on both sides, takes the format and has an empty open clip."""
+        self._check(self.lib.dsm_asr_clip_begin(self.h, int(slot), int(rate), int(fmt), int(flush_frames)))
+
+    def clip_push(self, slot, data):
+        """dsm_asr_clip_push: appends bytes (any count) to the slot's clip."""
+        data = bytes(data)
+        buf = np.frombuffer(data, dtype=np.uint8) if data else None
+        self._check(self.lib.dsm_asr_clip_push(self.h, int(slot), _ptr(buf), len(data)))
+
+    def clip_close(self, slot):
+        self._check(self.lib.dsm_asr_clip_close(self.h, int(slot)))
+
+    def clip_status(self, slot):
+        """ASR_CLIP_IDLE / RUNNING / WAITING / DONE."""
+        return self._check(self.lib.dsm_asr_clip_status(self.h, int(slot)))
+
+    def run(self, n_steps):
+        """dsm_asr_run: enqueues n_steps (1..ASR_RUN_MAX) steps of every slot with a clip; nothing is read back until collect()."""
+        self._check(self.lib.dsm_asr_run(self.h, int(n_steps)))
+
+    def collect(self):
+        """dsm_asr_collect: waits for the block.  Returns AsrBlock: stepped [n][B], text_token [n][B], vad_prs [n][heads][B],
+        logprob [n][B], msgs — per step the list poll_msgs would give —, word_scores — per step [(batch_idx, logprobs)] of its
+        Word messages —, status [B]."""
+        n, B, nh = ASR_RUN_MAX, self.B, self.cfg.extra_heads_num
+        stepped = np.zeros((n, B), dtype=np.uint8)
+        text = np.zeros((n, B), dtype=np.uint32)
+        prs = np.zeros((n, max(nh, 1), B), dtype=np.float32)
+        lp = np.zeros((n, B), dtype=np.float32)
+        status = np.zeros(B, dtype=np.int32)
+        cap = n * (2 * B + 1)  # a step gives at most a Step, and a Word and an EndWord per slot
+        msgs, step_of = (AsrMsg * cap)(), (C.c_int * cap)()
+        toks, tlps = np.zeros(cap * 8, dtype=np.uint32), np.zeros(cap * 8, dtype=np.float32)
+        blk = AsrBlockC(0, _ptr(stepped), _ptr(text), _ptr(prs) if nh else None, _ptr(lp), msgs, step_of, cap, 0, _ptr(toks),
+                        _ptr(tlps), toks.size, 0, _ptr(status))
+        self._check(self.lib.dsm_asr_collect(self.h, C.byref(blk)))
+        k = blk.n_steps
+        if blk.n_msgs > cap or blk.n_tokens > toks.size:
+            raise DsmError(f"collect: {blk.n_msgs} messages / {blk.n_tokens} tokens do not fit the arrays")
+        out, scores = [[] for _ in range(k)], [[] for _ in range(k)]
+        for i in range(blk.n_msgs):
+            m = msgs[i]
+            if m.kind == MSG_WORD:
+                out[step_of[i]].append(("Word", m.batch_idx, m.time, toks[m.tokens_offset:m.tokens_offset + m.n_tokens].tolist()))
+                scores[step_of[i]].append((m.batch_idx, tlps[m.tokens_offset:m.tokens_offset + m.n_tokens].copy()))
+            elif m.kind == MSG_END_WORD:
+                out[step_of[i]].append(("EndWord", m.batch_idx, m.time))
+            else:
+                out[step_of[i]].append(("Step", m.step_idx))
+        return AsrBlock(k, stepped[:k], text[:k], prs[:k, :nh], lp[:k], out, scores, status)
 
     # device-pointer variants (ints from torch.Tensor.data_ptr())
     def encode_step_dev(self, d_pcm, d_mask, d_codes):

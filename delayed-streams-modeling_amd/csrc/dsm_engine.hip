@@ -35,6 +35,7 @@
 #include "dsm_tts_slot_layout.h"
 #include "dsm_spm.h"
 #include "dsm_slot_xfer.inc"
+#include "dsm_asr_clip.h"
 
 static thread_local std::string g_create_error;
 
@@ -328,6 +329,43 @@ struct dsm_engine : DsmDevice {
   uint32_t* ingest_started[2] = {};
   uint8_t *ingest_raw_d[2] = {}, *ingest_raw_h[2] = {}, *ingest_pipe_raw_h[4] = {};
   std::mutex ingest_mu;  // the table's host mirrors (the worker's threads both reach them)
+  // clips (dsm_asr_set_clips; dsm_asr_clip.h, dsm_asr_clip.inc): the switch; the slots' clips [B][clip_cap] on the device and
+  // the pinned mirror pushes append to; the schedule's slots; a block's table (per slot AsrClipSlot, then frame [K][B] and mask
+  // [K][B]) on the device and pinned, its records [K][B (2 + heads)] likewise, and the steps of the block that waits for
+  // dsm_asr_collect (0: none).  All of it allocated by the first dsm_asr_set_clips(1).  clip_mu: the host side of the section.
+  std::atomic<bool> clips_on{false};
+  size_t clip_cap = 0;
+  uint8_t *clip_d = nullptr, *clip_h = nullptr;
+  std::vector<dsm_asr_clip::Slot> clip_slots;
+  uint8_t *clip_tab_d = nullptr, *clip_tab_h = nullptr;
+  uint32_t *clip_rec_d = nullptr, *clip_rec_h = nullptr;
+  int clip_blk_pending = 0;
+  std::mutex clip_mu;
+  // What the per-step calls and the slot resets ask first.  mask: the call's host mask, or null (a device mask, a reset).
+  // Nothing to ask while the section is off.
+  int clip_guard(const uint8_t* mask) {
+    if (!clips_on.load(std::memory_order_acquire)) return 0;
+    std::lock_guard<std::mutex> lk(clip_mu);
+    if (clip_blk_pending) { set_error("a block of %d steps waits for dsm_asr_collect", clip_blk_pending); return DSM_ERR_STATE; }
+    for (int b = 0; mask && b < B; ++b)
+      if (mask[b] && clip_slots[(size_t)b].status != DSM_ASR_CLIP_IDLE) {
+        set_error("slot %d has a clip: dsm_asr_run steps it (dsm_asr_reset_slot ends the clip)", b);
+        return DSM_ERR_STATE;
+      }
+    return 0;
+  }
+  // the same for the calls that name slots (snapshots carry no clip; a format belongs to its clip): none of them has a clip
+  int clip_guard_slots(const int* slots, int n, const char* who) {
+    if (!clips_on.load(std::memory_order_acquire)) return 0;
+    if (int rc = clip_guard(nullptr)) return rc;
+    std::lock_guard<std::mutex> lk(clip_mu);
+    for (int i = 0; i < n; ++i)
+      if (slots[i] >= 0 && slots[i] < B && clip_slots[(size_t)slots[i]].status != DSM_ASR_CLIP_IDLE) {
+        set_error("%s: slot %d has a clip (dsm_asr_reset_slot ends it)", who, slots[i]);
+        return DSM_ERR_STATE;
+      }
+    return 0;
+  }
   dsm_metrics metrics{};
   // run-ahead pipeline between the encoder thread and the model thread (dsm_mimi_encode_step_async /
   // dsm_asr_step_tokens_ticket): the reference's sync_channel(100) of PipelineMsg (srv/batched_asr.rs:291), here a ring of
@@ -1168,6 +1206,7 @@ int run_conv(DsmDevice* e, hipStream_t st, const ConvGeom& c, const float* cat, 
 #include "dsm_slot_state.inc"
 #include "dsm_text_bias.inc"
 #include "dsm_ingest.inc"
+#include "dsm_asr_clip.inc"
 #include "dsm_tts.inc"
 #include "dsm_tts_voice.inc"
 #include "dsm_tts_slot_state.inc"

@@ -591,8 +591,10 @@ int join_groups(dsm_engine* e) { return e->grp_busy ? join_groups(e, e->s_model,
 // Groups are NOT joined at the end of the step: each consumes only its own slots' state, so they free-run and one
 // group's attention (HBM-bound) overlaps another's GEMMs (MFMA-bound).  dsm_sync / the host-pointer entry points
 // synchronise every group stream.
-int lm_step(dsm_engine* e, hipStream_t st, const uint32_t* d_codes, const uint8_t* d_mask, uint32_t* d_text_out,
-            float* d_prs_out) {
+// after(g, stream): what a caller enqueues behind each group's step on that group's stream (dsm_asr_run's record launch).
+template <typename After>
+int lm_step_then(dsm_engine* e, hipStream_t st, const uint32_t* d_codes, const uint8_t* d_mask, uint32_t* d_text_out,
+                 float* d_prs_out, After&& after) {
   const size_t G = e->lm.groups.size();
   if (int rc = fork_groups(e, st, G)) return rc;
   // Staggered start (r02).  Groups that begin a step together stay in phase through all the layers — their attention
@@ -610,11 +612,17 @@ int lm_step(dsm_engine* e, hipStream_t st, const uint32_t* d_codes, const uint8_
     if (int rc = lm_group_head(e, gs, (int)g, d_codes, d_mask, stagger)) return rc;
     if (stagger && g + 1 < G) HIPCHK(hipEventRecord(e->ev_stagger[g], gs));
   }
-  if (int rc = run_groups(e, st, G, e->serialize_groups,
-                          [&](size_t g, hipStream_t gs) { return lm_group_rest(e, gs, (int)g, d_text_out, d_prs_out, stagger); }))
+  if (int rc = run_groups(e, st, G, e->serialize_groups, [&](size_t g, hipStream_t gs) {
+        if (int rc = lm_group_rest(e, gs, (int)g, d_text_out, d_prs_out, stagger)) return rc;
+        return after((int)g, gs);
+      }))
     return rc;
   if (G > 1) e->grp_busy = true;
   return 0;
+}
+int lm_step(dsm_engine* e, hipStream_t st, const uint32_t* d_codes, const uint8_t* d_mask, uint32_t* d_text_out,
+            float* d_prs_out) {
+  return lm_step_then(e, st, d_codes, d_mask, d_text_out, d_prs_out, [](int, hipStream_t) { return 0; });
 }
 
 int upload_pcm(dsm_engine* e, int side, hipStream_t st, const float* src, hipMemcpyKind kind) {
@@ -1119,6 +1127,7 @@ static int encode_host(dsm_engine* e, int side, hipStream_t st, const float* pcm
 
 int dsm_mimi_encode_step(dsm_engine* e, const float* pcm, const uint8_t* mask, uint32_t* codes_out, int* produced) {
   if (!e || !pcm || !mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(mask)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   HIPCHK(hipEventRecord(e->ev_a, e->s_enc));
@@ -1173,6 +1182,7 @@ static int step_tokens_host(dsm_engine* e, const uint32_t* d_codes, const uint8_
 int dsm_asr_step_tokens(dsm_engine* e, const uint32_t* codes, const uint8_t* mask, uint32_t* text_tokens_out,
                         float* vad_prs_out) {
   if (!e || !mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(mask)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   if (int rc = wait_group_inputs(e)) return rc;
@@ -1193,6 +1203,7 @@ int dsm_asr_step_tokens(dsm_engine* e, const uint32_t* codes, const uint8_t* mas
 int dsm_asr_step_pcm(dsm_engine* e, const float* pcm, const uint8_t* mask, uint32_t* codes_out,
                      uint32_t* text_tokens_out, float* vad_prs_out) {
   if (!e || !pcm || !mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(mask)) return rc;
   HIPCHK(hipSetDevice(e->device));
   if (int rc = ensure_model_side_mimi(e)) return rc;
   ApiShared api(e);
@@ -1222,6 +1233,7 @@ static int pipe_init(dsm_engine* e) {
 
 int dsm_mimi_encode_step_async(dsm_engine* e, const float* pcm, const uint8_t* mask, int* ticket) {
   if (!e || !pcm || !mask || !ticket) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(mask)) return rc;
   HIPCHK(hipSetDevice(e->device));
   // from here to the return no capture of the model thread is in progress (dsm_engine::api_mu): in particular not while
   // this thread waits on ev_consumed, an event last recorded on the stream that thread captures on
@@ -1270,6 +1282,7 @@ int dsm_mimi_encode_step_async(dsm_engine* e, const float* pcm, const uint8_t* m
 
 int dsm_asr_step_tokens_ticket(dsm_engine* e, int ticket, const uint8_t* mask, uint32_t* text_tokens_out, float* vad_prs_out) {
   if (!e || !mask || ticket < 0 || ticket >= dsm_engine::kPipe) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(mask)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   dsm_engine::PipeSlot& ps = e->pipe[ticket];
@@ -1451,6 +1464,11 @@ int dsm_asr_reset_slot(dsm_engine* e, int slot) {
     e->set_error("batch index out of range: %d >= %d", slot, e->B);  // core/asr.rs:258-260
     return DSM_ERR_INVALID;
   }
+  if (int rc = e->clip_guard(nullptr)) return rc;
+  if (e->clips_on.load(std::memory_order_acquire)) {  // a reset ends the slot's clip
+    std::lock_guard<std::mutex> lk(e->clip_mu);
+    e->clip_slots[(size_t)slot] = dsm_asr_clip::Slot();
+  }
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   e->items[slot] = HostItem();
@@ -1486,6 +1504,7 @@ int dsm_mimi_reset_slot(dsm_engine* e, int slot) {
     e->set_error("batch index out of range: %d >= %d", slot, e->B);
     return DSM_ERR_INVALID;
   }
+  if (int rc = e->clip_guard(nullptr)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   return reset_mimi_slot(e, 0, e->s_enc, slot);
@@ -1500,6 +1519,7 @@ int dsm_get_metrics(dsm_engine* e, dsm_metrics* out) {
 
 int dsm_mimi_encode_step_dev(dsm_engine* e, const float* d_pcm, const uint8_t* d_mask, uint32_t* d_codes_out) {
   if (!e || !d_pcm || !d_mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(nullptr)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   // the previous frame's codes must have been picked up by the model stream before they are overwritten
@@ -1518,6 +1538,7 @@ int dsm_mimi_encode_step_dev(dsm_engine* e, const float* d_pcm, const uint8_t* d
 int dsm_asr_step_tokens_dev(dsm_engine* e, const uint32_t* d_codes, const uint8_t* d_mask, uint32_t* d_text_tokens_out,
                             float* d_vad_prs_out) {
   if (!e || !d_mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(nullptr)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   if (int rc = wait_group_inputs(e)) return rc;
@@ -1544,6 +1565,7 @@ int dsm_asr_step_tokens_dev(dsm_engine* e, const uint32_t* d_codes, const uint8_
 int dsm_asr_step_pcm_dev(dsm_engine* e, const float* d_pcm, const uint8_t* d_mask, uint32_t* d_codes_out,
                          uint32_t* d_text_tokens_out, float* d_vad_prs_out) {
   if (!e || !d_pcm || !d_mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(nullptr)) return rc;
   HIPCHK(hipSetDevice(e->device));
   if (int rc = ensure_model_side_mimi(e)) return rc;
   ApiShared api(e);

@@ -129,6 +129,7 @@ int dsm_asr_set_ingest(dsm_engine* e, int on) {
 int dsm_asr_set_input_format(dsm_engine* e, int slot, int sample_rate_hz, int sample_format) {
   if (!e) return DSM_ERR_INVALID;
   if (slot < 0 || slot >= e->B) { e->set_error("batch index out of range: %d >= %d", slot, e->B); return DSM_ERR_INVALID; }
+  if (int rc = e->clip_guard_slots(&slot, 1, "set_input_format")) return rc;
   HIPCHK(hipSetDevice(e->device));
   std::unique_lock<std::shared_mutex> alone(e->api_mu);
   if (!e->ingest_on) { e->set_error("ingest is off: dsm_asr_set_ingest(engine, 1) comes first"); return DSM_ERR_STATE; }
@@ -155,6 +156,7 @@ int dsm_asr_input_format(dsm_engine* e, int slot, int* rate, int* fmt, int* fram
 
 int dsm_mimi_encode_step_raw(dsm_engine* e, const void* raw, size_t pitch_bytes, const uint8_t* mask, uint32_t* codes_out, int* produced) {
   if (!e || !raw || !mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(mask)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   if (int rc = ingest_check_call(e, pitch_bytes, mask)) return rc;
@@ -176,6 +178,7 @@ int dsm_mimi_encode_step_raw(dsm_engine* e, const void* raw, size_t pitch_bytes,
 int dsm_asr_step_raw(dsm_engine* e, const void* raw, size_t pitch_bytes, const uint8_t* mask, uint32_t* codes_out,
                      uint32_t* text_tokens_out, float* vad_prs_out) {
   if (!e || !raw || !mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(mask)) return rc;
   HIPCHK(hipSetDevice(e->device));
   {  // a refused call changes nothing: the check comes before the model side's Mimi is made
     ApiShared api(e);
@@ -195,6 +198,7 @@ int dsm_asr_step_raw(dsm_engine* e, const void* raw, size_t pitch_bytes, const u
 
 int dsm_mimi_encode_step_raw_async(dsm_engine* e, const void* raw, size_t pitch_bytes, const uint8_t* mask, int* ticket) {
   if (!e || !raw || !mask || !ticket) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(mask)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);  // as dsm_mimi_encode_step_async: no capture of the model thread is in progress from here to the return
   if (int rc = ingest_check_call(e, pitch_bytes, mask)) return rc;
@@ -235,6 +239,7 @@ int dsm_mimi_encode_step_raw_async(dsm_engine* e, const void* raw, size_t pitch_
 
 int dsm_mimi_encode_step_raw_dev(dsm_engine* e, const void* d_raw, size_t pitch_bytes, const uint8_t* d_mask, uint32_t* d_codes_out) {
   if (!e || !d_raw || !d_mask) return DSM_ERR_INVALID;
+  if (int rc = e->clip_guard(nullptr)) return rc;
   HIPCHK(hipSetDevice(e->device));
   ApiShared api(e);
   if (int rc = ingest_check_call(e, pitch_bytes, nullptr)) return rc;

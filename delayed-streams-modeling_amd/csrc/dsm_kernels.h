@@ -3236,3 +3236,85 @@ __global__ __launch_bounds__(256) void egress_resample_kernel(EgressArgs a) {
   pcm_keep_history(hist, egress_buf, DSM_FRAME_SIZE, d.taps, tid);
   if (tid == 0) a.started[b] = 1u;
 }
+
+// ------------------------------------------------------------------------------------------
+// Clips (dsm_asr_clip.h, which holds the definition; dsm_asr_run, dsm_asr_clip.inc): a slot's audio lies on the device in the
+// slot's own ingest format and is cut into frames here, one launch per step in front of ingest_resample_kernel.  Neither kernel
+// is part of a captured graph: the step's index k is a launch argument, every pointer an engine buffer.
+// ------------------------------------------------------------------------------------------
+struct AsrClipSlot {  // one per slot, uploaded with a block's table
+  uint32_t bytes;        // the clip's length as of the block (<= cap)
+  uint32_t frame_bytes;  // the slot's format's frame (<= pitch)
+  uint32_t silence;      // the byte behind the clip's end (dsm_asr_clip::silence_byte)
+  uint32_t reserved;
+};
+struct AsrClipArgs {
+  const uint8_t* clips;        // [B][cap] bytes, cap % 16 == 0, 16-byte aligned
+  size_t cap;
+  const AsrClipSlot* slots;    // [B]
+  const uint32_t* frame;       // [K][B] the block's table: frame index
+  const uint8_t* step_mask;    // [K][B] and mask
+  uint8_t* raw;                // [B][pitch] the raw staging ingest_resample_kernel reads, rows 16-byte aligned
+  size_t pitch;                // % 16 == 0
+  uint8_t* mask;               // [B] the step's mask (MimiState::mask)
+  int B;
+};
+
+// Step k of a block: slot b's frame — bytes [i fb, (i + 1) fb) of its clip, the silence byte from the clip's end on — into its
+// staging row, and the step's mask.  One 256-thread workgroup per slot; a slot that sits the step out writes its mask byte only.
+// A frame starts wherever i fb falls (882-byte frames at 11025 Hz mu-law, 3528-byte ones at 11025 Hz f32): 16-byte loads when
+// the source is 16-byte aligned, dwords when it is 4-byte aligned, bytes otherwise; the row is always stored 16 bytes at a time
+// where whole 16-byte groups of clip bytes or of silence lie.  Reads stay inside [0, bytes) of the slot's clip, writes inside
+// the first min(fb, pitch) bytes of its row.
+__global__ __launch_bounds__(256) void asr_clip_frame_kernel(AsrClipArgs a, int k) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const uint8_t on = a.step_mask[(size_t)k * a.B + b];
+  if (tid == 0) a.mask[b] = on;
+  if (!on) return;
+  const AsrClipSlot s = a.slots[b];
+  const uint32_t fb = s.frame_bytes < a.pitch ? s.frame_bytes : (uint32_t)a.pitch;
+  const uint64_t off = (uint64_t)a.frame[(size_t)k * a.B + b] * s.frame_bytes;
+  const uint32_t len = s.bytes < a.cap ? s.bytes : (uint32_t)a.cap;
+  const uint32_t have = off >= len ? 0u : (len - off < fb ? (uint32_t)(len - off) : fb);
+  const uint8_t* src = a.clips + (size_t)b * a.cap + (have ? (size_t)off : 0);
+  uint8_t* dst = (uint8_t*)__builtin_assume_aligned(a.raw + (size_t)b * a.pitch, 16);
+  const uint32_t whole = have & ~15u;  // clip bytes in whole 16-byte groups of the row
+  if (((uintptr_t)src & 15u) == 0) {
+    const uint4* s16 = (const uint4*)src;
+    for (uint32_t i = tid; i < whole / 16; i += 256) ((uint4*)dst)[i] = s16[i];
+  } else if (((uintptr_t)src & 3u) == 0) {
+    const uint32_t* s4 = (const uint32_t*)src;
+    for (uint32_t i = tid; i < whole / 16; i += 256) ((uint4*)dst)[i] = make_uint4(s4[4 * i], s4[4 * i + 1], s4[4 * i + 2], s4[4 * i + 3]);
+  } else {
+    for (uint32_t i = tid; i < whole / 16; i += 256) {
+      uint32_t w[4];
+      for (int j = 0; j < 4; ++j)
+        w[j] = (uint32_t)src[16 * i + 4 * j] | (uint32_t)src[16 * i + 4 * j + 1] << 8 | (uint32_t)src[16 * i + 4 * j + 2] << 16 |
+               (uint32_t)src[16 * i + 4 * j + 3] << 24;
+      ((uint4*)dst)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+  // the group the clip ends in, byte by byte: clip bytes, then silence up to the next 16-byte boundary or the frame's end
+  const uint32_t edge = (have + 15u) & ~15u, mid_end = edge < fb ? edge : fb;
+  for (uint32_t i = whole + tid; i < mid_end; i += 256) dst[i] = i < have ? src[i] : (uint8_t)s.silence;
+  // silence in whole groups, then the frame's last bytes
+  const uint32_t sil = s.silence * 0x01010101u, fill_end = fb & ~15u;
+  for (uint32_t i = mid_end / 16 + tid; i < fill_end / 16; i += 256) ((uint4*)dst)[i] = make_uint4(sil, sil, sil, sil);
+  for (uint32_t i = (fill_end > mid_end ? fill_end : mid_end) + tid; i < fb; i += 256) dst[i] = (uint8_t)s.silence;
+}
+
+// Behind a stream group's LM step, on that group's stream: what the step left for the group's slots [b0, b0 + nb) — text
+// token, log-probability (lp NULL: token scores are off, the quiet NaN) and VAD values prs [heads][B] — into row k of the
+// block's records (dsm_asr_clip::record_words words a row: text [B], logprob [B], prs [heads][B]).
+__global__ void asr_clip_record_kernel(uint32_t* __restrict__ rec, int k, const uint32_t* __restrict__ text, const float* __restrict__ lp,
+                                       const float* __restrict__ prs, int b0, int nb, int B, int heads) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb * (2 + heads)) return;
+  const int part = i / nb, b = b0 + i % nb;
+  uint32_t* row = rec + (size_t)k * B * (2 + heads);
+  uint32_t v;
+  if (part == 0) v = text[b];
+  else if (part == 1) v = lp ? dsm_f32_as_u32(lp[b]) : 0x7FC00000u;
+  else v = dsm_f32_as_u32(prs[(size_t)(part - 2) * B + b]);
+  row[(size_t)part * B + b] = v;
+}

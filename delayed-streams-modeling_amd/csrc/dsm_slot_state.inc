@@ -243,6 +243,7 @@ int dsm_slot_blob_info(const void* buf, size_t len, struct dsm_slot_blob_info* o
 int dsm_asr_export_slots(dsm_engine* e, const int* slots, int n, void* buf, size_t cap, size_t* needed) {
   if (!e) return DSM_ERR_INVALID;
   if (int rc = slot_check_list(e, e->B, slots, n, false, "export_slots")) return rc;
+  if (int rc = e->clip_guard_slots(slots, n, "export_slots")) return rc;
   SlotXfer& x = e->xfer;
   std::lock_guard<std::mutex> one(x.mu);
   slot_layout_build(e);
@@ -285,6 +286,7 @@ int dsm_asr_export_slots(dsm_engine* e, const int* slots, int n, void* buf, size
 int dsm_asr_import_slots(dsm_engine* e, const int* slots, int n, const void* buf, size_t len) {
   if (!e) return DSM_ERR_INVALID;
   if (int rc = slot_check_list(e, e->B, slots, n, true, "import_slots")) return rc;
+  if (int rc = e->clip_guard_slots(slots, n, "import_slots")) return rc;
   SlotXfer& x = e->xfer;
   std::lock_guard<std::mutex> one(x.mu);
   slot_layout_build(e);
@@ -330,6 +332,8 @@ int dsm_asr_move_slots(dsm_engine* src, const int* src_slots, dsm_engine* dst, c
   if (!src || !dst) return DSM_ERR_INVALID;
   if (int rc = slot_check_list(src, src->B, src_slots, n, false, "move_slots (source)")) return rc;
   if (int rc = slot_check_list(dst, dst->B, dst_slots, n, true, "move_slots (destination)")) { src->set_error("%s", dst->err.c_str()); return rc; }
+  if (int rc = src->clip_guard_slots(src_slots, n, "move_slots (source)")) return rc;
+  if (int rc = dst->clip_guard_slots(dst_slots, n, "move_slots (destination)")) { src->set_error("%s", dst->err.c_str()); return rc; }
   if (src == dst)
     for (int i = 0; i < n; ++i)
       for (int j = 0; j < n; ++j)

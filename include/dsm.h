@@ -1084,6 +1084,95 @@ int dsm_ingest_describe(int sample_rate_hz, int sample_format, uint32_t* words12
 int dsm_ingest_g711_table(int sample_format, int16_t* out256);
 int dsm_worker_set_input_rate(dsm_worker*, int slot, int hz);
 
+/* ---- clips: a slot's audio known beforehand, resident on the device in its own ingest format, K steps per visit (this project's
+ * own shape of the reference's request path, BatchedAsr::handle_query, srv/batched_asr.rs:810-854: decode, queue the audio, then
+ * silence, cut the queue into whole frames, collect Word / EndWord; the STT sibling of dsm_tts_run / dsm_tts_collect).  Off by
+ * default: nothing is allocated and every other call enqueues exactly what it enqueues without this section.  Definition
+ * (csrc/dsm_asr_clip.h, host only; the device side copies the bytes it names): a slot's CLIP is clip_bytes bytes in the slot's
+ * ingest format; FRAME i is bytes [i frame_bytes, (i + 1) frame_bytes) of the clip followed by endless silence — the byte 0x00
+ * for DSM_PCM_F32 and DSM_PCM_S16, 0xFF for DSM_PCM_MULAW (expands to 0), 0xD5 for DSM_PCM_ALAW (the idle code, expands to +8) —
+ * so a clip need not end on a frame or a sample.  With n_audio = ceil(clip_bytes / frame_bytes), a CLOSED slot takes frames
+ * 0 .. n_audio + flush_frames - 1, one per step, and is then DONE; an OPEN slot takes a frame only once all of its bytes were
+ * pushed, else it sits the step out (mask 0) and is WAITING.  The frames go through ingest_resample_kernel, the encoder-side
+ * Mimi and the LM exactly as through dsm_mimi_encode_step_raw_async + dsm_asr_step_tokens_ticket with the same rows and
+ * masks: codes, tokens, VAD values, scores, messages, HostItem and model_step_idx end bit for bit the same.
+ *   dsm_asr_set_clips     engine-wide switch, between steps.  On: turns ingest on if it is off and allocates [B][max] device
+ *     bytes for the clips (max_clip_bytes_per_slot, 1 .. 2^31, rounded up to 16), a pinned mirror of them that pushes append to,
+ *     the block's table and its records for DSM_ASR_RUN_MAX steps.  A second call with another size: DSM_ERR_STATE.  Off: the
+ *     calls below return DSM_ERR_STATE; DSM_ERR_STATE while a slot has a clip or a block waits.
+ *   dsm_asr_clip_begin    dsm_asr_reset_slot, dsm_mimi_reset_slot and dsm_asr_set_input_format(rate, fmt) for the slot, then the
+ *     slot has an empty open clip and is RUNNING.  flush_frames: silent frames behind the audio (the reference appends
+ *     asr_delay_in_tokens + a margin of frames of zeros behind a body).  DSM_ERR_STATE, nothing touched: the slot has a clip
+ *     already (dsm_asr_reset_slot ends one), a block waits, an encode ticket is outstanding.  DSM_ERR_INVALID: a rate or format
+ *     outside the ingest definition, flush_frames < 0.
+ *   dsm_asr_clip_push     appends n bytes (any count: a push need not end on a frame or a sample).  The copy rides the encoder
+ *     stream out of the pinned mirror, so the caller's buffer is free on return.  DSM_ERR_STATE, nothing changed: beyond
+ *     max_clip_bytes_per_slot, a closed slot, a slot without a clip, a block waits.
+ *   dsm_asr_clip_close    no more bytes: the clip's last, partial frame and the flush follow.  Closing twice is fine.
+ *   dsm_asr_run           n_steps (1 .. DSM_ASR_RUN_MAX) steps of every slot with a clip; enqueue only: no synchronise, no
+ *     download.  The host knows every slot's frame index and mask for all the steps (the schedule depends on no data) and
+ *     uploads them as one table; per step the encoder stream cuts the frames (asr_clip_frame_kernel), resamples and encodes,
+ *     the model stream takes codes AND mask in one hand-off and steps the LM into the engine's own buffers, and every stream
+ *     group records its slots' results behind its step.  Slots without a clip, WAITING and DONE slots are masked off.  The
+ *     captured graphs are the per-step calls' (no new variants, nothing settles again).  DSM_ERR_STATE, nothing touched: a
+ *     block waits for dsm_asr_collect, n_steps out of range, an encode ticket is outstanding.  While a block waits, the
+ *     stepping calls (dsm_mimi_encode_step*, dsm_asr_step_*), dsm_asr_reset_slot, dsm_mimi_reset_slot and
+ *     dsm_asr_set_input_format return DSM_ERR_STATE; between blocks the per-step calls serve the other slots (mask[b] = 1 on a
+ *     slot with a clip: DSM_ERR_STATE, nothing changed; the _dev calls, whose mask is on the device, are the caller's to keep
+ *     off clip slots).
+ *   dsm_asr_collect       the one synchronise of a block; fills the caller's arrays (any may be NULL) for the n_steps of the
+ *     block: stepped [n][B] (the slot took a frame in that step), text_token [n][B] and vad_prs [n][heads][B] (defined where
+ *     stepped is 1), logprob [n][B] (NaN while token scores are off), status [B] (DSM_ASR_CLIP_* after the block), and the
+ *     messages of every step — assemble_words replayed once per step over the records, so dsm_asr_poll_msgs afterwards holds the
+ *     last step's — with msg_step[i] = the index in the block of the step that msgs[i] belongs to, their tokens in msg_tokens
+ *     and the tokens' log-probabilities in msg_logprobs (tokens_offset counts from the block's first token).  n_msgs / n_tokens
+ *     are what the block produced; entries beyond msgs_cap / tokens_cap are dropped.  DSM_ERR_STATE when no block waits.
+ *   dsm_asr_clip_status   DSM_ASR_CLIP_* of the slot: as of the last dsm_asr_run, push or close.  dsm_asr_reset_slot ends a clip
+ *     (-> IDLE); its bytes are dropped.
+ *   dsm_asr_clip_frame_host  host only: frame `frame_index` of a clip in (rate, fmt) -> frame_out (the format's frame_bytes
+ *     bytes); returns frame_bytes, or DSM_ERR_INVALID with dsm_last_error(NULL) saying why.  clip may be NULL for 0 bytes.
+ *   dsm_asr_clip_host_*   host only, no device: the schedule dsm_asr_run goes through, for B slots with a cap per clip — begin
+ *     (frame_bytes from (rate, fmt)), push (a byte count), close, reset, status, and run: n_steps rows of frame [n][B] and
+ *     mask [n][B] (DSM_ERR_INVALID for n_steps outside 1 .. DSM_ASR_RUN_MAX).  Refusals as the engine's.
+ * Slot snapshots carry no clip: dsm_asr_export_slots / dsm_asr_move_slots of a slot with a clip return DSM_ERR_STATE.  The worker
+ * does not use this section: dsm_worker_send_body stays as it is. */
+#define DSM_ASR_RUN_MAX 16 /* steps per block: one row of the table and of the records each */
+enum { DSM_ASR_CLIP_IDLE = 0, DSM_ASR_CLIP_RUNNING = 1, DSM_ASR_CLIP_WAITING = 2, DSM_ASR_CLIP_DONE = 3 };
+typedef struct dsm_asr_block {
+  int n_steps;              /* out: steps in the block */
+  uint8_t* stepped;         /* [n][B] */
+  uint32_t* text_token;     /* [n][B] */
+  float* vad_prs;           /* [n][extra_heads_num][B] */
+  float* logprob;           /* [n][B] */
+  dsm_asr_msg* msgs;        /* [msgs_cap] */
+  int* msg_step;            /* [msgs_cap] */
+  int msgs_cap;
+  int n_msgs;               /* out */
+  uint32_t* msg_tokens;     /* [tokens_cap] */
+  float* msg_logprobs;      /* [tokens_cap] */
+  int tokens_cap;
+  int n_tokens;             /* out */
+  int* status;              /* [B] DSM_ASR_CLIP_* after the block */
+} dsm_asr_block;
+typedef struct dsm_asr_clip_host_state dsm_asr_clip_host_state;
+int dsm_asr_set_clips(dsm_engine*, int on, size_t max_clip_bytes_per_slot);
+int dsm_asr_clip_begin(dsm_engine*, int slot, int sample_rate_hz, int sample_format, int flush_frames);
+int dsm_asr_clip_push(dsm_engine*, int slot, const void* bytes, size_t n);
+int dsm_asr_clip_close(dsm_engine*, int slot);
+int dsm_asr_run(dsm_engine*, int n_steps);
+int dsm_asr_collect(dsm_engine*, dsm_asr_block* out);
+int dsm_asr_clip_status(dsm_engine*, int slot);
+int dsm_asr_clip_frame_host(const void* clip, size_t clip_bytes, int sample_rate_hz, int sample_format, uint64_t frame_index,
+                            void* frame_out);
+dsm_asr_clip_host_state* dsm_asr_clip_host_new(int batch_size, size_t max_clip_bytes_per_slot);
+void dsm_asr_clip_host_free(dsm_asr_clip_host_state*);
+int dsm_asr_clip_host_begin(dsm_asr_clip_host_state*, int slot, int sample_rate_hz, int sample_format, int flush_frames);
+int dsm_asr_clip_host_push(dsm_asr_clip_host_state*, int slot, size_t n);
+int dsm_asr_clip_host_close(dsm_asr_clip_host_state*, int slot);
+int dsm_asr_clip_host_reset(dsm_asr_clip_host_state*, int slot);
+int dsm_asr_clip_host_status(dsm_asr_clip_host_state*, int slot);
+int dsm_asr_clip_host_run(dsm_asr_clip_host_state*, int n_steps, uint32_t* frame /*[n][B]*/, uint8_t* mask /*[n][B]*/);
+
 /* ---- egress: per-slot TTS output sample rate and sample format, resampled and encoded on the device (this project's own: the
  * reference's TTS sockets send 24 kHz f32, srv/tts.rs:528-544).  The ingest section run the other way — the same rates, the same
  * DSM_PCM_* formats, the same filter family.  Off by default: nothing is allocated and every other call enqueues exactly what it
